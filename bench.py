@@ -11,10 +11,19 @@ N GPUs = N processes (torchrun), each with its own SAs chosen so that
 fnv1_32(spi) mod N == rank (SPI-hash sharding, no collective on the data path);
 per-GPU work is fixed (weak scaling) and value = all ranks' bytes / max time.
 
-Prints ONE JSON line (rank 0) with the metric, a roofline object for the
-dominant kernel (algorithmic bytes / HIP-event time on the launch stream) and a
-cpu_baseline object (the oracle's cryptosoft-shaped restatement, timed on this
-host's cores on a bounded sample of the same records).
+Prints ONE JSON line (rank 0) with the metric and a roofline object for the
+dominant kernel (algorithmic bytes / HIP-event time of the timed steps on the
+launch stream).  A plain run does nothing else: set up, warm up, time the
+steps, print.  --full adds every side measurement to the line: the measured
+HBM copy ceiling and the committed rocprofv3 traffic, the other decrypt mode,
+the packed-output, encrypt and PCIe end-to-end legs, and the cpu_baseline /
+cpu_openssl objects (the oracle's cryptosoft-shaped restatement and OpenSSL
+EVP, timed on this host's cores on a bounded sample of the same records); the
+--no-* options drop single legs from a --full run.
+--dump-outputs DIR writes what the last timed step returned to its caller
+(the per-record status bytes and a fixed, seeded sample of the decrypted
+bytes) as DIR/<name>.npy; the inputs are the same from run to run, so two
+builds can be compared output for output.
 """
 import argparse
 import json
@@ -96,6 +105,25 @@ def hbm_copy_gbs(arena, reps=5):
     ms = e0.elapsed_time(e1) / reps
     del dst
     return 2 * arena.numel() / (ms * 1e-3) / 1e9
+
+
+DUMP_SAMPLE = 1 << 23          # bytes of the decrypted buffer kept by --dump-outputs (32 MB as float32)
+
+
+def dump_outputs(path, rank, status, buf):
+    """--dump-outputs: what the last timed step handed its caller, as float32
+    .npy files under `path`: status.npy, every record's status byte, and
+    decrypted_sample.npy, the bytes of the decrypted buffer at DUMP_SAMPLE
+    fixed positions (seeded, sorted; the whole buffer when it is smaller).
+    Rank r > 0 of a multi-GPU run writes <name>_rank<r>.npy."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    sfx = "_rank%d" % rank if rank else ""
+    np.save(os.path.join(path, "status%s.npy" % sfx), status.cpu().numpy().astype(np.float32))
+    if buf.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0xE5B000D0).integers(0, buf.numel(), DUMP_SAMPLE))
+        buf = buf[torch.from_numpy(idx).to(buf.device)]
+    np.save(os.path.join(path, "decrypted_sample%s.npy" % sfx), buf.cpu().numpy().astype(np.float32))
 
 
 def plan_packets(cfg, rank, world, rng):
@@ -219,6 +247,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="cfg1", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement (HBM copy ceiling, profile "
+                         "traffic, the other decrypt mode, packed-output, encrypt and PCIe legs, CPU baselines); "
+                         "the --no-* options below drop single legs of such a run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (status bytes, a seeded sample of the "
+                         "decrypted bytes) as DIR/<name>.npy")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every core of this process's CPU share (affinity and cgroup quota)")
     ap.add_argument("--cpu-runs", type=int, default=5, help="cpu_baseline: median of this many runs")
@@ -257,6 +292,8 @@ def main():
     inplace = not args.out_of_place
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 and not args.dry_plan:
+        ap.error("--steps must be >= 1")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -353,7 +390,8 @@ def main():
     encrypt_batch(drv, arena, desc, n, status, grouped=grouped)     # build valid ESP records (untimed)
     torch.cuda.synchronize()
     assert int((status != 0).sum()) == 0, "record generation failed"
-    out = None if inplace else torch.empty(total + args.out_pad * n, dtype=torch.uint8, device=dev)
+    # (zeroed, so the bytes no record covers are the same from run to run: --dump-outputs)
+    out = None if inplace else torch.zeros(total + args.out_pad * n, dtype=torch.uint8, device=dev)
     # In place, every timed step needs ciphertext: step k decrypts its own copy
     # of the records (`arena` itself stays ciphertext for the side legs), as
     # many copies as K steps when HBM holds them (288 GB: 20 x 1.5 GB), else
@@ -415,6 +453,9 @@ def main():
         ev_ms += ev0.elapsed_time(ev1)
         done += seg
     assert knobs or int((status != 0).sum()) == 0, "decrypt/verify failed in the timed steps"
+    if args.dump_outputs:
+        # the last timed step's results: step seg-1 of the last segment
+        dump_outputs(args.dump_outputs, rank, status, bufs[(seg - 1) % len(bufs)] if inplace else out)
     del bufs
     dt, all_pkt_bytes = aggregate(dist, world, dt, pkt_bytes, dev)
     ms_per_step = dt * 1e3 / args.steps
@@ -443,12 +484,6 @@ def main():
     # against the guide's measured copy ceiling (a torch copy here reaches less)
     result["roofline"]["guide_copy_gbs"] = GUIDE_COPY_GBS
     result["roofline"]["frac_of_guide_copy"] = round(achieved / GUIDE_COPY_GBS, 4)
-    try:
-        copy = hbm_copy_gbs(arena)
-        result["roofline"]["hbm_copy_gbs"] = round(copy, 1)
-        result["roofline"]["frac_of_copy"] = round(achieved / copy, 4)
-    except Exception as e:                       # informational only
-        log("hbm copy measurement skipped: %s" % e)
     result["config"]["world"] = world
     result["config"]["packets_per_rank"] = per_rank(dist, world, rank, n, dev)
     result["config"]["device_per_rank"] = per_rank(dist, world, rank, local, dev)
@@ -458,30 +493,33 @@ def main():
         result["config"]["inplace_copies"] = ncopy
     kernel = launched_kernel(cfg, inplace)
     result["roofline"]["kernel"] = kernel
-    result["roofline"].update(profile_traffic(args.config, inplace, kernel, kern_ms))
-    if not args.no_inplace_leg:
-        leg = side_leg(drv, arena, desc, n, status, grouped, stream, pkt_bytes,
-                       algo_bytes, world, dist, launched_kernel(cfg, not inplace), not inplace)
-        result["inplace" if not inplace else "out_of_place"] = leg
-
-    if not args.no_packed_leg and cfg["alg"] == "gcm":
-        result["packed_out"] = packed_leg(drv, arena, desc, d, n, status, grouped, stream, pkt_bytes,
-                                          algo_bytes, world, dist)
-
-    if not args.no_encrypt_leg:
-        result["encrypt"] = encrypt_leg(drv, arena, desc, n, status, grouped, stream, pkt_bytes, world, dist, cfg)
-
-    if not args.no_e2e:
-        result["e2e_pcie"] = e2e_leg(drv, arena, desc, d, n, pkt_bytes,
-                                     args, world, dist)
-    if rank == 0 and world == 1 and not args.no_cpu:
-        result["cpu_baseline"] = cpu_baseline(arena, d, sids, keys, args,
-                                              n, cfg)
+    if args.full:
+        # every side measurement: runs of their own, after the timed steps
         try:
-            result["cpu_openssl"] = cpu_openssl(arena, d, sids, keys, args,
-                                                n, cfg)
-        except Exception as e:                   # informational only (needs tools/libossl_esp.so)
-            log("cpu_openssl skipped: %s" % e)
+            copy = hbm_copy_gbs(arena)
+            result["roofline"]["hbm_copy_gbs"] = round(copy, 1)
+            result["roofline"]["frac_of_copy"] = round(achieved / copy, 4)
+        except Exception as e:                       # informational only
+            log("hbm copy measurement skipped: %s" % e)
+        result["roofline"].update(profile_traffic(args.config, inplace, kernel, kern_ms))
+        if not args.no_inplace_leg:
+            leg = side_leg(drv, arena, desc, n, status, grouped, stream, pkt_bytes,
+                           algo_bytes, world, dist, launched_kernel(cfg, not inplace), not inplace)
+            result["inplace" if not inplace else "out_of_place"] = leg
+        if not args.no_packed_leg and cfg["alg"] == "gcm":
+            result["packed_out"] = packed_leg(drv, arena, desc, d, n, status, grouped, stream, pkt_bytes,
+                                              algo_bytes, world, dist)
+        if not args.no_encrypt_leg:
+            result["encrypt"] = encrypt_leg(drv, arena, desc, n, status, grouped, stream, pkt_bytes, world, dist,
+                                            cfg)
+        if not args.no_e2e:
+            result["e2e_pcie"] = e2e_leg(drv, arena, desc, d, n, pkt_bytes, args, world, dist)
+        if rank == 0 and world == 1 and not args.no_cpu:
+            result["cpu_baseline"] = cpu_baseline(arena, d, sids, keys, args, n, cfg)
+            try:
+                result["cpu_openssl"] = cpu_openssl(arena, d, sids, keys, args, n, cfg)
+            except Exception as e:                   # informational only (needs tools/libossl_esp.so)
+                log("cpu_openssl skipped: %s" % e)
     if rank == 0:
         print(json.dumps(result), flush=True)
     drv.close()

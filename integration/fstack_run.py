@@ -3,7 +3,7 @@
 executable that runs the reference's own opencrypto framework
 (integration/fstack_run/, INTEGRATION.md section 4, "Running it").
 
-    python integration/fstack_run.py build [--ref /root/reference] [--work DIR]
+    make -C oracle fstack        (python integration/fstack_run.py build [--ref DIR] [--work DIR])
 
 1. integration/fstack_build_check.py's build_kernel(): the F-Stack tree
    copied and patched (apply_fstack.sh), every kernel-domain object of an
@@ -15,10 +15,13 @@ executable that runs the reference's own opencrypto framework
 3. the host domain: fstack_run/host_main.c and fstack_run/host_stubs.c (the
    DPDK-side symbols, integration/fstack_build_check.py "host_blocked"),
    with either the real host shim ff_gpucrypto_host.c + libespgpu.so
-   (integration/fstack_crypto_run_gpu) or the oracle stand-in
-   fstack_run/oracle_engine.c (integration/fstack_crypto_run_cpu).
-The executables are built here (they need /root/reference) and, like the
-.so files, travel to the GPU box untracked.
+   (oracle/_ref/fstack_crypto_run_gpu) or the oracle stand-in
+   fstack_run/oracle_engine.c (oracle/_ref/fstack_crypto_run_cpu).
+The executables hold code compiled from the F-Stack tree, so they go where
+every build product of it goes: oracle/_ref/, untracked, built where that
+tree exists (oracle/Makefile's `fstack` target) and carried from there to a
+GPU host that has none.  They find libespgpu.so and liboracle.so relative to
+themselves ($ORIGIN), wherever the repository lies.
 
 pack_requests() / read_results() are the file formats host_main.c reads and
 writes (used by tests/test_fstack_run.py).
@@ -32,8 +35,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 RUN = os.path.join(HERE, "fstack_run")
-EXE_CPU = os.path.join(HERE, "fstack_crypto_run_cpu")
-EXE_GPU = os.path.join(HERE, "fstack_crypto_run_gpu")
+OUT = os.path.join(ROOT, "oracle", "_ref")
+EXE_CPU = os.path.join(OUT, "fstack_crypto_run_cpu")
+EXE_GPU = os.path.join(OUT, "fstack_crypto_run_gpu")
 EXPORTS = ["ffst_find_driver", "ffst_newsession", "ffst_freesession", "ffst_request", "ffst_dispatch",
            "ffst_result", "ffst_ndone", "ffst_redispatch", "ffst_free"]
 SELFTEST_RULE = """
@@ -83,9 +87,11 @@ def build(ref, work, jobs=8):
         objs_h[name] = o
     espgpu = os.path.join(ROOT, "f-stack_amd")
     orc = os.path.join(ROOT, "oracle")
-    common = ["-no-pie", ro, objs_h["stubs"], "-L" + espgpu, "-lespgpu", "-Wl,-rpath," + espgpu, "-lpthread", "-lm"]
+    os.makedirs(OUT, exist_ok=True)
+    common = ["-no-pie", ro, objs_h["stubs"], "-L" + espgpu, "-lespgpu", "-Wl,-rpath,$ORIGIN/../../f-stack_amd",
+              "-lpthread", "-lm"]
     run(["gcc", "-o", EXE_CPU, objs_h["main_cpu"], objs_h["oracle_engine"]] + common +
-        ["-L" + orc, "-loracle", "-Wl,-rpath," + orc])
+        ["-L" + orc, "-loracle", "-Wl,-rpath,$ORIGIN/.."])
     run(["gcc", "-o", EXE_GPU, objs_h["main_gpu"], objs_h["shim"]] + common)
     return EXE_CPU, EXE_GPU
 

@@ -22,7 +22,8 @@ crypto.c (integration/fstack_run/host_main.c):
 The CPU executable (fstack_crypto_run_cpu) has the oracle stand-in
 (integration/fstack_run/oracle_engine.c) behind the host shim's interface;
 the GPU one (fstack_crypto_run_gpu) the real shim and libespgpu.so.  Both
-are built here, where /root/reference exists, and travel to the GPU box.
+are built into oracle/_ref/ where the F-Stack tree exists (oracle/Makefile's
+`fstack` target) and reach a GPU host without that tree with oracle/_ref/.
 """
 import os
 import subprocess
@@ -232,6 +233,8 @@ def _check(res, workload):
 
 
 HAVE_REF = os.path.isdir("/root/reference/lib")
+MISSING_GPU_EXE = ("oracle/_ref/fstack_crypto_run_gpu missing: run __graft_entry__.build() where the F-Stack tree "
+                   "exists and bring oracle/_ref/ along")
 
 
 @pytest.fixture(scope="module")
@@ -245,7 +248,7 @@ def test_fstack_opencrypto_with_gpucrypto_cpu(built, workload, tmp_path):
     """The CPU executable (oracle stand-in behind the host shim interface)."""
     exe = built[0]
     if not os.path.exists(exe):
-        pytest.skip("needs the F-Stack tree to build integration/fstack_crypto_run_cpu")
+        pytest.skip("needs the F-Stack tree to build oracle/_ref/fstack_crypto_run_cpu")
     _check(_run(exe, workload, tmp_path), workload)
 
 
@@ -255,10 +258,10 @@ def test_fstack_opencrypto_with_gpucrypto_gpu(workload, tmp_path):
     real host shim and libespgpu.so on the MI355X, against cryptosoft run in
     the same process, the DPDK known answers and the oracle."""
     exe = FR.EXE_GPU
-    # built where the F-Stack tree exists (__graft_entry__.build) and shipped
-    # with the tree: a GPU run without it has lost the only F-Stack-level GPU
+    # built where the F-Stack tree exists (__graft_entry__.build) and carried
+    # in oracle/_ref/: a GPU run without it has lost the only F-Stack-level GPU
     # check, which must show as a failure, not a skip
-    assert os.path.exists(exe), "integration/fstack_crypto_run_gpu missing: run __graft_entry__.build() where /root/reference exists"
+    assert os.path.exists(exe), MISSING_GPU_EXE
     _check(_run(exe, workload, tmp_path), workload)
 
 
@@ -267,7 +270,7 @@ def test_fstack_gpu_failure_cpu(built, workload, tmp_path):
     oracle stand-in fails with the requests staged)."""
     exe = built[0]
     if not os.path.exists(exe):
-        pytest.skip("needs the F-Stack tree to build integration/fstack_crypto_run_cpu")
+        pytest.skip("needs the F-Stack tree to build oracle/_ref/fstack_crypto_run_cpu")
     res = _run(exe, workload, tmp_path, fail=True)
     _check(res, workload)
     _check_failure(res, workload)
@@ -279,7 +282,7 @@ def test_fstack_gpu_failure_gpu(workload, tmp_path):
     engine's next launch fails (set_tuning "fault" 1) with every request
     staged; each completes once with EIO, later requests move to cryptosoft."""
     exe = FR.EXE_GPU
-    assert os.path.exists(exe), "integration/fstack_crypto_run_gpu missing: run __graft_entry__.build() where /root/reference exists"
+    assert os.path.exists(exe), MISSING_GPU_EXE
     res = _run(exe, workload, tmp_path, fail=True)
     _check(res, workload)
     _check_failure(res, workload)

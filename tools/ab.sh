@@ -5,7 +5,8 @@
 # $OUT (default gpurun_out/ab.jsonl).
 #
 #   bash tools/ab.sh [-r ROUNDS] [-c "cfg1 cfg4"] [-o OUT] [-x "bench args"] [-e] CAND...
-# (-e: also the encrypt leg; its kernel time is summarised as enc_ms)
+# (-e: also the encrypt leg, a bench.py --full run with the other legs off; its
+# kernel time is summarised as enc_ms)
 #
 # CAND = name=LIB[@key=val,key=val][%bench-arg]: LIB a libespgpu.so (e.g. abl/<name>/libespgpu.so
 # from tools/variant.sh, or f-stack_amd/libespgpu.so), the optional @ list set_tuning
@@ -14,7 +15,7 @@
 set -euo pipefail
 ROUNDS=3; CFGS="cfg1"; OUT=gpurun_out/ab.jsonl; XARGS=""; ENC=--no-encrypt-leg
 while getopts "r:c:o:x:e" o; do
-  case $o in r) ROUNDS=$OPTARG ;; c) CFGS=$OPTARG ;; o) OUT=$OPTARG ;; x) XARGS=$OPTARG ;; e) ENC="" ;; *) exit 2 ;; esac
+  case $o in r) ROUNDS=$OPTARG ;; c) CFGS=$OPTARG ;; o) OUT=$OPTARG ;; x) XARGS=$OPTARG ;; e) ENC=--full ;; *) exit 2 ;; esac
 done
 shift $((OPTIND - 1))
 [ $# -ge 1 ] || { echo "usage: tools/ab.sh [-r N] [-c cfgs] [-o out] [-x args] name=lib[@k=v,...] ..." >&2; exit 2; }

@@ -19,7 +19,10 @@ for p in ${PROFS-cfg1 cfg2 cfg3 cfg4 cfg0 cfg1_oop}; do
   esac
 done
 cp profiles/${TAG}_*.json profiles/pmc_*.json gpurun_out/profiles/ 2>/dev/null || true
+# (--full: every leg and the CPU baselines; lines go to $BENCH_OUT, default bench_out/)
+BOUT=${BENCH_OUT:-bench_out}
+mkdir -p "$BOUT"
 for c in ${BENCHES-cfg1 cfg0 cfg2 cfg3 cfg4}; do
-  timeout -k 10 300 python bench.py --config $c > gpurun_out/bench_${TAG}_$c.json 2> gpurun_out/bench_${TAG}_$c.err
+  timeout -k 10 300 python bench.py --full --config $c > "$BOUT/bench_${TAG}_$c.json" 2> "$BOUT/bench_${TAG}_$c.err"
   echo "bench $c done"
 done
