@@ -1287,12 +1287,13 @@ __global__ __launch_bounds__(WG) void gcm_kernel(GcmParams p) {
       // Session check per record: a chunk is one session (planner), but a
       // caller-grouped batch (implicit chunks) is trusted only this far: a
       // record whose own session is not this chunk's AEAD session is EINVAL
-      // here (do_group: valid requires desc.sa == sa) unless it is an ETA
-      // record, which the ETA kernel owns.
+      // here (do_group: valid requires desc.sa == sa) unless it is an ETA or
+      // DIGEST (AH) record, which the ETA / digest kernel owns.
       if (mode != ESPGPU_CSP_MODE_AEAD) {
         if (have && (tid & (S - 1)) == 0) {
           const uint32_t rsa = p.desc[di].sa;
-          const bool eta = rsa < p.nsas && p.sas[rsa].mode == ESPGPU_CSP_MODE_ETA;
+          const bool eta = rsa < p.nsas && (p.sas[rsa].mode == ESPGPU_CSP_MODE_ETA ||
+                                          p.sas[rsa].mode == ESPGPU_CSP_MODE_DIGEST);
           if (!eta) {
             p.status[di] = ESPGPU_EINVAL;
             if (MODE != 1 && p.trailer) p.trailer[di] = 0;
@@ -1386,12 +1387,13 @@ __device__ __forceinline__ void burst_chunk(const GcmParams &p, uint8_t *lds, ui
   }
   const uint32_t nr = ss.nr, flags = ss.flags, mlen = ss.mlen;
   if (ss.mode != ESPGPU_CSP_MODE_AEAD) {
-    // as gcm_kernel: EINVAL unless the ETA kernel's record
+    // as gcm_kernel: EINVAL unless the ETA / digest kernel's record
     for (uint32_t r = (uint32_t)tid; r < count; r += WG) {
       const uint32_t pos = start + r;
       const uint32_t di = p.order ? p.order[pos] : pos;
       const uint32_t rsa = p.desc[di].sa;
-      const bool eta = rsa < p.nsas && p.sas[rsa].mode == ESPGPU_CSP_MODE_ETA;
+      const bool eta = rsa < p.nsas && (p.sas[rsa].mode == ESPGPU_CSP_MODE_ETA ||
+                                          p.sas[rsa].mode == ESPGPU_CSP_MODE_DIGEST);
       if (!eta) {
         p.status[di] = ESPGPU_EINVAL;
         if (DIR == 0 && p.trailer) p.trailer[di] = 0;

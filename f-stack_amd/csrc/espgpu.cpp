@@ -8,6 +8,7 @@
 //   newsession    cryptosoft.c:1309-1409, swcr_setup_gcm :1087, _cipher :976, _auth :1003
 //   freesession   cryptosoft.c:1412
 //   process       cryptosoft.c:1429-1441 (swcr_process) -> swcr_gcm :465 / swcr_eta :874
+//                 / swcr_authcompute :317 (CSP_MODE_DIGEST: AH, xform_ah.c)
 //   completion    crypto_done, crypto.c:1802
 #include <hip/hip_runtime.h>
 #include <sched.h>
@@ -157,7 +158,7 @@ struct Slot {
   uint32_t desc_off = 0, stat_off = 0;      // set by flush
   int32_t sid0 = -1;                        // session of the first record
   bool mixed = false;                       // more than one session staged
-  uint32_t kinds = 0;                       // 1: GCM records, 2: ETA records
+  uint32_t kinds = 0;                       // 1: GCM records, 2: ETA records, 4: DIGEST (AH) records
   std::vector<Pending> reqs;             // reserved to batch_records: no per-record allocation
   std::vector<espgpu_seg> segpool;       // segment lists of the staged requests
   hipEvent_t in_done = nullptr, k0 = nullptr, k1 = nullptr, kout = nullptr, done = nullptr;
@@ -193,13 +194,14 @@ struct espgpu_ctx {
   uint8_t *d_gtab = nullptr;
   uint2 *d_tpair = nullptr, *d_dpair = nullptr;
   uint8_t *d_isbox = nullptr;
-  uint32_t *d_queue = nullptr;   // work-queue regions (kQueueRegionWords apart): GCM, ETA, ETA aux (self-resetting)
+  uint32_t *d_queue = nullptr;   // work-queue regions (kQueueRegionWords apart): GCM, ETA, ETA aux, DIGEST (self-resetting)
   std::vector<Session> sessions;
   std::vector<DevSA> h_sas;
   // ETA sessions: all, and by kernel: narrow-hash (SHA-1 / SHA2-256) CBC and
   // CTR, wide-hash (SHA2-384/512) CBC and CTR
   int n_eta = 0, n_cbc = 0, n_ctr = 0, n_wcbc = 0, n_wctr = 0;
   int n_gcm = 0;                 // live AEAD (GCM) sessions
+  int n_dig = 0, n_dig_wide = 0; // live DIGEST (AH) sessions: all, and the HMAC-SHA2-384/512 ones
   bool plan_dirty = true;        // planner key counts not known to be zero (plan_scan re-zeroes them)
   int n_whash = 0;   // ETA sessions with HMAC-SHA2-384/512 (the wide-hash two-pass kernels)
   // GCM lanes per record: 0 = by batch size, 4 or 8 forced (set_tuning
@@ -698,7 +700,9 @@ int xfer_reserve(espgpu_ctx *c, Slot &s, uint32_t need) {
 
 // Launch the crypto kernels for one batch of device-resident records.
 // kinds: which kernels the batch needs (1 GCM, 2 ETA); the device-resident
-// entry points do not know and pass both.
+// entry points do not know and pass both, with 8: DIGEST (AH) records under
+// the batch path's semantics.  4: a process-path batch with DIGEST requests
+// (swcr_authcompute's semantics: DigestParams::op 2).
 // The self-staging lists of a small single-session GCM process batch
 // (GcmParams::xin / xout / hstat).
 struct StageLists {
@@ -709,11 +713,11 @@ struct StageLists {
 
 int run_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n,
               uint8_t *d_status, uint8_t *d_out, uint32_t flags, int encrypt, hipStream_t st,
-              uint32_t *d_trailer = nullptr, uint32_t kinds = 3, const StageLists *stage = nullptr,
+              uint32_t *d_trailer = nullptr, uint32_t kinds = 1 | 2 | 8, const StageLists *stage = nullptr,
               uint32_t out_stride = 0) {
   if (c->failed) return ESPGPU_EIO;
   if (n == 0) return 0;
-  if (out_stride && c->n_eta > 0)
+  if (out_stride && (c->n_eta > 0 || c->n_dig > 0))
     return fail(c, ESPGPU_ENOTSUP, "packed output serves contexts with GCM sessions only");
   if (c->fault & ESPGPU_FAULT_LAUNCH) {
     c->fault &= ~(uint32_t)ESPGPU_FAULT_LAUNCH;
@@ -808,6 +812,25 @@ int run_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32
                    (c->n_wctr > 0 ? 8 : 0) | (c->n_whash > 0 ? 16 : 0);
     if (launch_eta(q, encrypt, ek, grid, st))
       return fail(c, ESPGPU_EIO, "ETA kernel launch failed");
+  }
+  // AH digest sessions: launched only while the context has some
+  if (c->n_dig > 0 && (kinds & 12)) {
+    DigestParams g{};
+    g.arena = d_arena;
+    g.icv_out = p.out;
+    g.desc = d_desc;
+    g.order = p.order;
+    g.chunks = p.chunks;
+    g.nchunks = p.nchunks;
+    g.queue = c->d_queue + 3 * kQueueRegionWords;
+    g.trailer = p.trailer;
+    g.n = n;
+    g.sas = c->d_sas;
+    g.status = d_status;
+    g.nsas = nsas;
+    g.op = (kinds & 4) ? 2u : (encrypt ? 1u : 0u);
+    if (launch_digest(g, c->n_dig > c->n_dig_wide, c->n_dig_wide > 0, grid, st))
+      return fail(c, ESPGPU_EIO, "digest kernel launch failed");
   }
   HIPCHK(c, hipEventRecord(c->ev_last, st));
   c->last_st = st;
@@ -943,8 +966,21 @@ void espgpu_fini(espgpu_ctx *c) {
   delete c;
 }
 
-// swcr_probesession + check_csp restricted to the ESP ciphers this engine serves.
-int espgpu_probesession(const espgpu_session_params *csp) {
+// Whether the driver bids for AH (CSP_MODE_DIGEST) sessions: set_tuning
+// "ah_offer" (process-wide, like the probe itself), else FF_GPUCRYPTO_AH in
+// the environment.  Off by default, and decided here rather than only in the
+// F-Stack shim: a binary linked before the engine knew the mode forwards every
+// csp to the probe, and must keep AH on cryptosoft under a newer library.
+static int g_ah_offer = -1;                // -1: the environment decides
+static bool ah_offered() {
+  if (g_ah_offer >= 0) return g_ah_offer != 0;
+  const char *e = getenv("FF_GPUCRYPTO_AH");
+  return e && atoi(e) > 0;
+}
+
+// swcr_probesession + check_csp restricted to what this engine serves:
+// ESPGPU_PROBE_HARDWARE or ESPGPU_EINVAL (espgpu_newsession's check).
+static int probe_caps(const espgpu_session_params *csp) {
   if (!csp) return ESPGPU_EINVAL;
   const int supported_flags = ESPGPU_CSP_F_SEPARATE_AAD | ESPGPU_CSP_F_ESN;
   if (csp->csp_flags & ~supported_flags) return ESPGPU_EINVAL;
@@ -999,17 +1035,46 @@ int espgpu_probesession(const espgpu_session_params *csp) {
       if (csp->csp_flags & ESPGPU_CSP_F_SEPARATE_AAD) return ESPGPU_EINVAL;
       return ESPGPU_PROBE_HARDWARE;
     }
+    case ESPGPU_CSP_MODE_DIGEST: {
+      // AH (ah_init, xform_ah.c:231-246): an HMAC over the whole packet,
+      // check_csp's CSP_MODE_DIGEST rules (crypto.c:792-821: no cipher
+      // algorithm, key or IV) and swcr_auth_supported.  CRYPTO_NULL_HMAC,
+      // RIPEMD, plain hashes and AES-GMAC (which ah_init sets up with
+      // csp_ivlen 0, refused by cryptosoft itself) stay with cryptosoft.
+      if (csp->csp_cipher_alg != 0 || csp->csp_cipher_klen != 0 || csp->csp_cipher_key != nullptr ||
+          csp->csp_ivlen != 0)
+        return ESPGPU_EINVAL;
+      if (csp->csp_flags & ~ESPGPU_CSP_F_ESN) return ESPGPU_EINVAL;
+      int hashlen = 0;
+      switch (csp->csp_auth_alg) {
+        case ESPGPU_CRYPTO_SHA1_HMAC: hashlen = 20; break;
+        case ESPGPU_CRYPTO_SHA2_256_HMAC: hashlen = 32; break;
+        case ESPGPU_CRYPTO_SHA2_384_HMAC: hashlen = 48; break;
+        case ESPGPU_CRYPTO_SHA2_512_HMAC: hashlen = 64; break;
+      }
+      if (!hashlen || csp->csp_auth_klen <= 0 || !csp->csp_auth_key) return ESPGPU_EINVAL;
+      if (csp->csp_auth_mlen > hashlen || (csp->csp_auth_mlen & 3)) return ESPGPU_EINVAL;
+      return ESPGPU_PROBE_HARDWARE;
+    }
     default:
       return ESPGPU_EINVAL;
   }
 }
 
+// The driver's bid: what the engine serves, AH only when it is offered.
+int espgpu_probesession(const espgpu_session_params *csp) {
+  const int r = probe_caps(csp);
+  if (r == ESPGPU_PROBE_HARDWARE && csp->csp_mode == ESPGPU_CSP_MODE_DIGEST && !ah_offered()) return ESPGPU_EINVAL;
+  return r;
+}
+
 int espgpu_newsession(espgpu_ctx *c, const espgpu_session_params *csp, int32_t *sid_out) {
   if (!c || !csp || !sid_out) return ESPGPU_EINVAL;
   if (c->failed) return ESPGPU_EIO;                  // (espgpu_last_error keeps the cause)
-  int pr = espgpu_probesession(csp);
+  int pr = probe_caps(csp);                          // (served whether or not the driver bids for it)
   if (pr >= 0) return fail(c, ESPGPU_EINVAL, "session parameters not supported");
-  const bool null_cipher = csp->csp_cipher_alg == ESPGPU_CRYPTO_NULL_CBC;
+  const bool digest = csp->csp_mode == ESPGPU_CSP_MODE_DIGEST;
+  const bool null_cipher = csp->csp_cipher_alg == ESPGPU_CRYPTO_NULL_CBC || digest;
   if (!csp->csp_cipher_key && !null_cipher)
     return fail(c, ESPGPU_EINVAL, "per-request keys are not supported; session key required");
   int slot = -1;
@@ -1045,7 +1110,7 @@ int espgpu_newsession(espgpu_ctx *c, const espgpu_session_params *csp, int32_t *
     hc::ghash_tables(h, tabs.data());
     HIPCHK(c, hipMemcpy(c->d_gtab + (size_t)slot * kGhTableBytes, tabs.data(), kGhTableBytes, hipMemcpyHostToDevice));
   } else {
-    const bool auth = csp->csp_mode == ESPGPU_CSP_MODE_ETA;
+    const bool auth = csp->csp_mode == ESPGPU_CSP_MODE_ETA || digest;
     const int aalg = auth ? csp->csp_auth_alg : 0;
     const bool sha256 = aalg == ESPGPU_CRYPTO_SHA2_256_HMAC;
     const bool wide = aalg == ESPGPU_CRYPTO_SHA2_384_HMAC || aalg == ESPGPU_CRYPTO_SHA2_512_HMAC;
@@ -1083,15 +1148,18 @@ int espgpu_newsession(espgpu_ctx *c, const espgpu_session_params *csp, int32_t *
   s.flags = csp->csp_flags;
   s.mlen = (int)sa.mlen;
   s.klen = csp->csp_cipher_klen;
-  const bool eta_kind = csp->csp_mode != ESPGPU_CSP_MODE_AEAD;
+  const bool eta_kind = csp->csp_mode != ESPGPU_CSP_MODE_AEAD && !digest;
   s.ctr = eta_kind && csp->csp_cipher_alg == ESPGPU_CRYPTO_AES_ICM;
   s.null = eta_kind && null_cipher;
-  s.whash = eta_kind && (sa.aalg == ESPGPU_CRYPTO_SHA2_384_HMAC || sa.aalg == ESPGPU_CRYPTO_SHA2_512_HMAC);
+  s.whash = (eta_kind || digest) && (sa.aalg == ESPGPU_CRYPTO_SHA2_384_HMAC || sa.aalg == ESPGPU_CRYPTO_SHA2_512_HMAC);
   s.wide = s.whash || (eta_kind && (sa.aalg == 0 || null_cipher));
   if (eta_kind) {
     c->n_eta++;
     eta_count(c, s)++;
     c->n_whash += s.whash ? 1 : 0;
+  } else if (digest) {
+    c->n_dig++;
+    c->n_dig_wide += s.whash ? 1 : 0;
   } else {
     c->n_gcm++;
   }
@@ -1130,7 +1198,10 @@ void espgpu_freesession(espgpu_ctx *c, int32_t sid) {
     if (c->launched) hipEventSynchronize(c->ev_last);
   }
   const Session &fs = c->sessions[sid];
-  if (fs.mode != ESPGPU_CSP_MODE_AEAD) {
+  if (fs.mode == ESPGPU_CSP_MODE_DIGEST) {
+    c->n_dig--;
+    c->n_dig_wide -= fs.whash ? 1 : 0;
+  } else if (fs.mode != ESPGPU_CSP_MODE_AEAD) {
     c->n_eta--;
     eta_count(c, fs)--;
     c->n_whash -= fs.whash ? 1 : 0;
@@ -1166,11 +1237,14 @@ int espgpu_process(espgpu_ctx *c, const espgpu_req *r, int hint) {
   size_t total = 0;
   for (int i = 0; i < r->nsegs; ++i) total += r->segs[i].len;
   const bool gcm = ses.mode == ESPGPU_CSP_MODE_AEAD, cipher_only = ses.mode == ESPGPU_CSP_MODE_CIPHER;
+  // AH (CSP_MODE_DIGEST): the record is the hashed range itself, no header,
+  // and the ICV field lies inside it
+  const bool dig = ses.mode == ESPGPU_CSP_MODE_DIGEST;
   // ICV bytes in the record: the session's (possibly truncated) mlen, 16/12/8
   // for GCM (cryptosoft.c:1112-1117), 12 or 20 for HMAC-SHA1, 16 for
   // HMAC-SHA2-256-128, none without auth.  IV: 8 for GCM / CTR, none for
   // ESP-NULL (ivsize 0), else 16.
-  const int ivlen = (gcm || ses.ctr) ? 8 : ses.null ? 0 : 16, hlen = 8 + ivlen, alen = ses.mlen;
+  const int ivlen = (gcm || ses.ctr) ? 8 : ses.null ? 0 : 16, hlen = dig ? 0 : 8 + ivlen, alen = dig ? 0 : ses.mlen;
   const int plen = r->crp_payload_length;
   int aad_start = cipher_only ? r->crp_payload_start - hlen : r->crp_aad_start;
   // ESP shape checks
@@ -1182,7 +1256,18 @@ int espgpu_process(espgpu_ctx *c, const espgpu_req *r, int hint) {
     return reject(ESPGPU_EINVAL);
   uint8_t hdr[8];
   uint32_t esn_hi = 0, salt = 0;
-  if (gcm) {
+  if (dig) {
+    // swcr_authcompute's request as ah_input / ah_output build it
+    // (xform_ah.c:613-664, :972-1047): no AAD, COMPUTE or VERIFY, the digest
+    // field inside the payload range at a multiple of 4
+    const int doff = r->crp_digest_start - r->crp_payload_start;
+    if (r->crp_aad || r->crp_aad_length != 0 || op == 1 || plen > 65535 || doff < 0 || (doff & 3) ||
+        doff + ses.mlen > plen)
+      return reject(ESPGPU_EINVAL);
+    if (ses.flags & ESPGPU_CSP_F_ESN) esn_hi = be32(r->crp_esn);
+    salt = (uint32_t)doff | ((r->crp_op & ESPGPU_CRYPTO_OP_VERIFY_DIGEST) ? kDigVerifyBit : 0u);
+    aad_start = r->crp_payload_start;
+  } else if (gcm) {
     if (!(r->crp_flags & ESPGPU_CRYPTO_F_IV_SEPARATE)) return reject(ESPGPU_EINVAL);   // cryptosoft.c:496
     if (r->crp_aad) {
       if (!(ses.flags & ESPGPU_CSP_F_SEPARATE_AAD) || r->crp_aad_length != 12) return reject(ESPGPU_EINVAL);
@@ -1226,7 +1311,7 @@ int espgpu_process(espgpu_ctx *c, const espgpu_req *r, int hint) {
   }
   if (alen && r->crp_digest_start != r->crp_payload_start + plen) return reject(ESPGPU_EINVAL);
   const uint32_t rlen = (uint32_t)(hlen + plen + alen);
-  if (rlen > 65535 || (rlen & 3) || rlen + 16 > c->cfg.batch_bytes) return reject(ESPGPU_EINVAL);
+  if (rlen > 65535 || (!dig && (rlen & 3)) || rlen + 16 > c->cfg.batch_bytes) return reject(ESPGPU_EINVAL);
   // Zero-copy when the whole record lies in one segment of registered memory
   // with the layout the kernels read (the staged path takes a GCM record's
   // header and IV from crp_aad / crp_iv: they must equal the buffer's).
@@ -1263,13 +1348,19 @@ int espgpu_process(espgpu_ctx *c, const espgpu_req *r, int hint) {
     pd.nspan = 2;
     pd.span[1] = {(uint32_t)r->crp_digest_start, (uint32_t)(hlen + plen), (uint32_t)ses.mlen};
   }
+  if (dig) {
+    // COMPUTE: the mlen digest bytes and nothing else; VERIFY: nothing
+    const bool verify = (salt & kDigVerifyBit) != 0;
+    pd.nspan = verify ? 0 : 1;
+    pd.span[0] = {(uint32_t)r->crp_digest_start, salt & ~kDigVerifyBit, verify ? 0u : (uint32_t)ses.mlen};
+  }
   espgpu_desc d;
   d.off4 = 0;
   d.len = (uint16_t)rlen;
   d.sa = (uint16_t)sid;
   d.esn_hi = esn_hi;
   d.salt = salt;
-  const uint8_t kind = gcm ? 1 : 2;
+  const uint8_t kind = gcm ? 1 : dig ? 4 : 2;
   // Where it goes: the filling slot; the overflow when the slots are all in
   // flight (or the overflow already holds requests: arrival order is kept);
   // else ERESTART.
@@ -1875,10 +1966,17 @@ int espgpu_decrypt_host(espgpu_ctx *c, const uint8_t *h_arena, uint64_t arena_by
                         const espgpu_desc *h_desc, uint32_t n, uint8_t *h_status, uint8_t *h_out,
                         uint32_t chunk, uint32_t flags) {
   if (c && c->failed) return ESPGPU_EIO;
+  if (c && c->n_dig > 0)
+    return fail(c, ESPGPU_ENOTSUP, "the host pipeline does not serve contexts with DIGEST sessions");
   return batch_rc(c, host_pipeline(c, h_arena, arena_bytes, h_desc, n, h_status, h_out, chunk, flags, 0));
 }
 
 int espgpu_set_tuning(espgpu_ctx *c, const char *key, int value) {
+  if (key && !strcmp(key, "ah_offer")) {           // process-wide: no context needed
+    if (value < -1 || value > 1) return ESPGPU_EINVAL;
+    g_ah_offer = value;
+    return 0;
+  }
   if (!c || !key) return ESPGPU_EINVAL;
   if (!strcmp(key, "grid")) { c->cfg.grid = (uint32_t)value; return 0; }
   if (!strcmp(key, "gcm_lanes")) {

@@ -1,6 +1,6 @@
 // espgpu_internal.h — device-side data layouts shared by the host runtime
-// (espgpu.cpp) and the HIP kernels (esp_gcm.hip, esp_cbc.hip, plan.hip,
-// xfer.hip).
+// (espgpu.cpp) and the HIP kernels (esp_gcm.hip, esp_cbc.hip, esp_ah.hip,
+// plan.hip, xfer.hip).
 #pragma once
 #include <stdint.h>
 
@@ -19,11 +19,12 @@ namespace espgpu {
 //   (hmac_init_pad, crypto.c:413-441).  CSP_MODE_CIPHER sessions are ETA
 //   sessions to the kernels (mode ETA) with aalg 0 and mlen 0: the cipher pass
 //   alone; calg ESPGPU_CRYPTO_NULL_CBC is the identity cipher (no key, no IV).
+// DIGEST (AH): aalg, mlen, flags and ipad/opad as ETA; no cipher fields.
 struct DevSA {
   uint32_t rk[64];
   uint32_t dk[64];
   uint32_t nr;
-  uint32_t mode;    // ESPGPU_CSP_MODE_AEAD / _ETA, 0 = free slot
+  uint32_t mode;    // ESPGPU_CSP_MODE_AEAD / _ETA / _DIGEST, 0 = free slot
   uint32_t flags;   // csp_flags
   uint32_t mlen;    // ICV bytes compared / written
   uint32_t ipad[16]; // ETA: HMAC chaining states after the ipad / opad key
@@ -97,7 +98,8 @@ struct GcmParams {
 };
 
 // Work-queue regions (ctx d_queue): one per kernel family, kQueueRegionWords
-// apart.  Word 0 = the ticket counter, word 1 = retired count.
+// apart (GCM, ETA, ETA aux, DIGEST).  Word 0 = the ticket counter, word 1 =
+// retired count.
 constexpr uint32_t kQueueRegionWords = 1024;
 
 struct EtaParams {
@@ -116,6 +118,29 @@ struct EtaParams {
   const uint8_t *isbox;           // inverse S-box (256 B)
   uint8_t *status;
   uint32_t nsas;
+};
+
+// AH digest sessions (esp_ah.hip digest_kernel): lane = record HMAC over the
+// whole record, any byte length.
+constexpr uint32_t kDigVerifyBit = 0x80000000u;   // driver path: desc.salt bit 31 = VERIFY_DIGEST
+struct DigestParams {
+  const uint8_t *arena;           // records (read only)
+  uint8_t *icv_out;               // computed ICVs go to icv_out + record offset + ICV offset
+  const espgpu_desc *desc;
+  const uint32_t *order;          // planner permutation or nullptr (implicit)
+  const Chunk *chunks;            // units are the ETA-range chunks [nchunks[0], nchunks[1])
+  const uint32_t *nchunks;
+  uint32_t *queue;                // [0] ticket, [1] retired waves (self-resetting)
+  uint32_t *trailer;              // verify: ESPGPU_TR_VALID or 0 per record, or nullptr
+  uint32_t n;
+  const DevSA *sas;
+  uint8_t *status;
+  uint32_t nsas;
+  // 0: batch verify (ICV field read as zeros, compared, nothing written);
+  // 1: batch compute (ICV field read as zeros, ICV written);
+  // 2: driver path, swcr_authcompute to the letter: the record hashed as it
+  //    stands; per record compute, or verify if desc.salt has kDigVerifyBit
+  uint32_t op;
 };
 
 // esp_input_cb's checks on the last 3 plaintext bytes (xform_esp.c:597-630),
@@ -207,6 +232,8 @@ int set_eta_opts(uint32_t opts);
 // bit 1 = such CTR (or ESP-NULL) ones, bits 2 / 3 = SHA2-384/512 CBC / CTR
 // ones, bit 4 = any SHA2-384/512 session
 int launch_eta(const EtaParams &p, int encrypt, int kinds, int grid, void *stream);
+// wide: the context has HMAC-SHA2-384/512 DIGEST sessions (a second launch)
+int launch_digest(const DigestParams &p, int narrow, int wide, int grid, void *stream);
 int launch_replay_check(const uint8_t *arena, espgpu_desc *desc, uint32_t n, const espgpu_replay *rp,
                         uint32_t nrp, const uint32_t *bitmap, uint8_t *rstatus, void *stream);
 int launch_xfer(const XferSpan *spans, uint32_t nspans, const uint8_t *status, void *stream);

@@ -49,7 +49,8 @@ __device__ __forceinline__ uint32_t key_of(const espgpu_desc &d, const DevSA *sa
   const uint32_t sa = d.sa;
   if (sa >= nsas) return 4 * nsas;
   const uint32_t mode = sas[sa].mode;
-  if (mode == ESPGPU_CSP_MODE_ETA) return 4 * nsas + 1 + sa;
+  // (a DIGEST (AH) SA is keyed as an ETA one: one key per SA, 64-record chunks)
+  if (mode == ESPGPU_CSP_MODE_ETA || mode == ESPGPU_CSP_MODE_DIGEST) return 4 * nsas + 1 + sa;
   if (mode != ESPGPU_CSP_MODE_AEAD) return 4 * nsas;
   // largest class first: with the kernels' dynamic chunk queues this is
   // longest-processing-time-first scheduling

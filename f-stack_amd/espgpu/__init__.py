@@ -8,6 +8,7 @@ from ._lib import lib  # noqa: F401
 from .opencrypto import (CryptoFramework, GpuCryptoDriver, crypto_session_params,  # noqa: F401
                          cryptop)
 from .esp import CBC_SHA1, GCM, SecAssoc  # noqa: F401
+from .ah import AhSecAssoc  # noqa: F401
 
 __all__ = ["lib", "CryptoFramework", "GpuCryptoDriver", "crypto_session_params", "cryptop",
-           "SecAssoc", "GCM", "CBC_SHA1"]
+           "SecAssoc", "GCM", "CBC_SHA1", "AhSecAssoc"]

@@ -13,6 +13,7 @@ HEADER = os.path.join(os.path.dirname(PKG_ROOT), "include", "espgpu.h")
 
 # constants (cryptodev.h values, see include/espgpu.h)
 CSP_MODE_CIPHER = 2
+CSP_MODE_DIGEST = 3
 CSP_MODE_AEAD = 4
 CSP_MODE_ETA = 5
 CSP_F_SEPARATE_AAD = 0x2

@@ -13,6 +13,9 @@
  *   AES-CBC or AES-CTR with no auth, or NULL
  *     (CSP_MODE_CIPHER)                         -> swcr_encdec   cryptosoft.c:101-284
  *                                                  (NULL: swcr_null, :91-95)
+ * and for AH (netipsec/xform_ah.c):
+ *   HMAC-SHA1 or HMAC-SHA2-256 / -384 / -512 over the whole packet
+ *     (CSP_MODE_DIGEST)                         -> swcr_authcompute cryptosoft.c:317-382
  * Every entry point is plain C: integers, pointers, sizes.  No exceptions,
  * no C++ or torch types cross it.  Errors are errno values, as in opencrypto.
  * One espgpu_ctx per lcore thread (thread-compatible, not thread-safe), the
@@ -46,6 +49,7 @@ extern "C" {
 
 /* ---- constants, numerically identical to freebsd/opencrypto/cryptodev.h ---- */
 #define ESPGPU_CSP_MODE_CIPHER      2        /* cryptodev.h:362: ESP without auth */
+#define ESPGPU_CSP_MODE_DIGEST      3        /* cryptodev.h:363: AH (xform_ah.c ah_init) */
 #define ESPGPU_CSP_MODE_AEAD        4        /* cryptodev.h:364 */
 #define ESPGPU_CSP_MODE_ETA         5        /* cryptodev.h:365 */
 #define ESPGPU_CSP_F_SEPARATE_AAD   0x0002   /* cryptodev.h:370 */
@@ -61,6 +65,7 @@ extern "C" {
 #define ESPGPU_CRYPTO_OP_DECRYPT    0x0      /* cryptodev.h:598 */
 #define ESPGPU_CRYPTO_OP_ENCRYPT    0x1
 #define ESPGPU_CRYPTO_OP_VERIFY_DIGEST 0x2
+#define ESPGPU_CRYPTO_OP_COMPUTE_DIGEST 0x0  /* cryptodev.h:603 */
 #define ESPGPU_CRYPTO_F_IV_SEPARATE 0x0200   /* cryptodev.h:470 */
 #define ESPGPU_CRYPTO_HINT_MORE     0x1      /* cryptodev.h:612 */
 #define ESPGPU_PROBE_HARDWARE       (-100)   /* CRYPTODEV_PROBE_HARDWARE, cryptodev.h:345 */
@@ -142,7 +147,9 @@ struct espgpu_desc {
 	uint16_t len;           /* ESP record length: SPI|SN|IV|payload|ICV          */
 	uint16_t sa;            /* session slot (espgpu_newsession's id)             */
 	uint32_t esn_hi;        /* high 32 bits of the ESN (SAs with CSP_F_ESN/SEP)  */
-	uint32_t salt;          /* GCM salt / AES-CTR nonce = crp_iv[0..3], in memory order */
+	uint32_t salt;          /* GCM salt / AES-CTR nonce = crp_iv[0..3], in memory order;
+	                           DIGEST (AH) SAs: the byte offset of the ICV field inside
+	                           the record, a multiple of 4 with salt + mlen <= len */
 };
 
 struct espgpu_config {
@@ -195,7 +202,11 @@ int  espgpu_health(espgpu_ctx *ctx);
 
 /* ---- opencrypto driver methods (cryptodev_if.m) ---- */
 /* CRYPTODEV_PROBESESSION (cryptodev_if.m:72-75): ESPGPU_PROBE_HARDWARE or EINVAL.
- * Host-only; no device needed. */
+ * Host-only; no device needed.  The driver's bid: every session kind the
+ * engine serves, except that AH (CSP_MODE_DIGEST) sessions are bid for only
+ * when offered -- set_tuning "ah_offer" 1, or FF_GPUCRYPTO_AH=1 in the
+ * environment -- so that a binary linked before the engine knew the mode
+ * keeps AH on cryptosoft.  espgpu_newsession serves them either way. */
 int  espgpu_probesession(const struct espgpu_session_params *csp);
 /* CRYPTODEV_NEWSESSION (cryptodev_if.m:93-97): expands keys (AES schedule,
  * GHASH power tables, HMAC ipad/opad states) into the device SA table. */
@@ -220,7 +231,12 @@ int  espgpu_session_room(espgpu_ctx *ctx);
  * in one segment of memory registered with espgpu_register_host is not
  * copied by the CPU: the GPU reads it and writes the results back in place.
  * Malformed requests complete with crp_etype = EINVAL via poll(), as
- * crypto_done would.  `hint` (CRYPTO_HINT_MORE) is accepted and ignored:
+ * crypto_done would.  A DIGEST (AH) session's request is swcr_authcompute's:
+ * the message is [crp_payload_start, +crp_payload_length) as it stands (1 ..
+ * 65535 bytes, any byte length, no AAD), then crp_esn for ESN sessions; the
+ * digest field [crp_digest_start, +mlen) lies inside it at a multiple of 4
+ * from crp_payload_start.  COMPUTE_DIGEST writes those mlen bytes and nothing
+ * else; VERIFY_DIGEST writes nothing and completes with 0 or EBADMSG.  `hint` (CRYPTO_HINT_MORE) is accepted and ignored:
  * staged requests launch at espgpu_flush (once per RX burst) or when a
  * staging slot fills. */
 int  espgpu_process(espgpu_ctx *ctx, const struct espgpu_req *req, int hint);
@@ -259,6 +275,16 @@ int  espgpu_get_stats(espgpu_ctx *ctx, struct espgpu_stats *st);
  * its ciphertext: AES-GCM in one pass that XORs the keystream back over a
  * failed record, CBC/CTR + HMAC verifying before it decrypts).
  * encrypt: payload encrypted in place, ICV written.
+ * DIGEST (AH) SAs: one record is one packet, len = the hashed bytes (any
+ * value 1..65535, off4 the packet start), salt = the byte offset of the ICV
+ * field inside it (a multiple of 4, salt + mlen <= len; else EINVAL).  In
+ * both directions the ICV field reads as zeros while the packet is hashed
+ * (ah_input's save-and-zero, ah_output's zeroing); the mutable IP header
+ * fields are the caller's business (ah_massage_headers).  encrypt: the ICV is
+ * written at salt, status 0, nothing else moves.  decrypt (and _trailer): the
+ * stored ICV is compared (ah_input_cb), status 0 or EBADMSG, and nothing is
+ * written to d_arena or d_out, in place or out of place; the trailer word is
+ * ESPGPU_TR_VALID alone, or 0.  A batch may mix GCM, ETA and DIGEST SAs.
  * `flags`: ESPGPU_BATCH_GROUPED if d_desc is already grouped by session with
  * at most one session per aligned run of 256 records (skips the device
  * planner; records of another session than their run's come back EINVAL).
@@ -287,7 +313,7 @@ int  espgpu_encrypt_batch(espgpu_ctx *ctx, uint8_t *d_arena, const struct espgpu
  * (swcr_gcm releases no plaintext for it, cryptosoft.c:600-603).  For a
  * device-side consumer of the plaintext; the line-aligned stores make the
  * kernel ≈ 4-6 % faster than the record layout's.  GCM
- * contexts only: ENOTSUP when the context has ETA sessions.  No esp_input_cb
+ * contexts only: ENOTSUP when the context has ETA or DIGEST sessions.  No esp_input_cb
  * trailer words. */
 int  espgpu_decrypt_batch_packed(espgpu_ctx *ctx, uint8_t *d_arena, const struct espgpu_desc *d_desc,
                                  uint32_t n, uint8_t *d_status, uint8_t *d_out, uint32_t out_stride,
@@ -317,7 +343,8 @@ int  espgpu_decrypt_batch_trailer(espgpu_ctx *ctx, uint8_t *d_arena,
  * or hipHostRegister), descriptors in ascending arena order; `chunk` records per
  * step (0 = 65536).  Step k's H2D, step k-1's kernels and step k-2's D2H run
  * concurrently on three HIP streams.  Plaintext lands in h_out at the same
- * offsets; returns when everything is back. */
+ * offsets; returns when everything is back.  ENOTSUP while the context has
+ * DIGEST (AH) sessions: their records produce no output to carry back. */
 int  espgpu_decrypt_host(espgpu_ctx *ctx, const uint8_t *h_arena, uint64_t arena_bytes,
                          const struct espgpu_desc *h_desc, uint32_t n, uint8_t *h_status,
                          uint8_t *h_out, uint32_t chunk, uint32_t flags);
@@ -403,6 +430,9 @@ float espgpu_last_kernel_ms(espgpu_ctx *ctx);
  *               completion query of an in-flight batch returns an error) and
  *               _STUCK (the next batch launched is never seen to complete, so
  *               it meets the deadline); each bit is consumed once;
+ *   "ah_offer"  whether espgpu_probesession bids for AH (CSP_MODE_DIGEST)
+ *               sessions: 1 / 0, or -1 (the default) to let FF_GPUCRYPTO_AH in
+ *               the environment decide; process-wide, `ctx` may be NULL;
  *   "gcm_opts" / "eta_opts" measurement knobs that skip work on purpose
  *               (results wrong): only in libespgpu_knobs.so, ENOTSUP in the
  *               product library unless 0.

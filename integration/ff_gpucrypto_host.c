@@ -18,6 +18,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "espgpu.h"
 
@@ -37,6 +38,14 @@ static espgpu_ctx *g_ctx;          /* one F-Stack process = one lcore = one ctx 
  * get a cryptop for (xform_esp.c:348-354). */
 static int g_noqueue;
 #define FF_GPUCRYPTO_OVERFLOW_MB 256
+/* AH offload (CSP_MODE_DIGEST sessions, xform_ah.c ah_init): the engine
+ * serves them, this binding offers them only when asked -- FF_GPUCRYPTO_AH=1
+ * in the environment of ff_gpucrypto_host_init_proc, or
+ * ff_gpucrypto_host_tune("ah", 1).  Off by default: AH SAs stay with
+ * cryptosoft, as before the engine knew the mode.  The engine's probe keeps
+ * the same default on the same variable (set_tuning "ah_offer"), so a shim
+ * built before this switch existed behaves alike. */
+static int g_ah;
 
 void ff_gpucrypto_host_set_noqueue(int on)
 {
@@ -60,11 +69,12 @@ int ff_gpucrypto_host_init(int gpu)
  * handed to a resident kernel through pinned host memory instead of a launch
  * each (a 32-record burst 42 -> 25 us).  Off by default:
  * the resident kernel keeps N CUs while bursts arrive (it exits after 20 ms
- * without one). */
+ * without one).
+ * FF_GPUCRYPTO_AH=1 offers AH sessions to the GPU (off by default). */
 int ff_gpucrypto_host_init_proc(int proc_id)
 {
 	int n = espgpu_device_count(), e;
-	const char *door;
+	const char *door, *ah;
 
 	if (n <= 0)
 		return ESPGPU_ENODEV;
@@ -74,6 +84,9 @@ int ff_gpucrypto_host_init_proc(int proc_id)
 		door = getenv("FF_GPUCRYPTO_DOOR");
 		if (door && atoi(door) > 0)
 			espgpu_set_tuning(g_ctx, "door", atoi(door));
+		ah = getenv("FF_GPUCRYPTO_AH");
+		if (ah)
+			g_ah = atoi(ah) > 0;
 	}
 	return e;
 }
@@ -119,6 +132,14 @@ int ff_gpucrypto_host_stats(struct espgpu_stats *st)
 
 int ff_gpucrypto_host_tune(const char *key, int value)
 {
+	/* "ah" is the binding's own switch, not an engine knob */
+	if (key && strcmp(key, "ah") == 0) {
+		if (value != 0 && value != 1)
+			return ESPGPU_EINVAL;
+		g_ah = value;
+		/* the engine's own bid follows (espgpu_probesession) */
+		return espgpu_set_tuning(g_ctx, "ah_offer", value);
+	}
 	return g_ctx ? espgpu_set_tuning(g_ctx, key, value) : ESPGPU_ENXIO;
 }
 
@@ -137,6 +158,9 @@ int ff_gpucrypto_host_probe(const struct espgpu_session_params *csp)
 
 	if (ff_gpucrypto_host_failed())
 		return ESPGPU_ENXIO;
+	/* AH sessions only when the offload is switched on */
+	if (csp && csp->csp_mode == ESPGPU_CSP_MODE_DIGEST && !g_ah)
+		return ESPGPU_EINVAL;
 	r = espgpu_probesession(csp);
 	/* a full SA table declines here, so that crypto_newsession selects
 	 * cryptosoft rather than failing the SA in CRYPTODEV_NEWSESSION

@@ -157,10 +157,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("cmd", choices=["build"])
     ap.add_argument("--ref", default="/root/reference")
-    ap.add_argument("--work", default="/tmp/fstack_run_build")
+    ap.add_argument("--work", default=None, help="scratch directory (default: a fresh temporary one, removed afterwards)")
     ap.add_argument("-j", type=int, default=8)
     a = ap.parse_args()
-    print(build(a.ref, a.work, a.j))
+    if a.work:
+        print(build(a.ref, a.work, a.j))
+        return
+    # a directory of this run's own: a fixed path under /tmp may belong to
+    # another user, and a build that cannot replace it leaves old executables
+    import shutil
+    import tempfile
+    top = tempfile.mkdtemp(prefix="fstack_run_build_")
+    try:
+        print(build(a.ref, os.path.join(top, "w"), a.j))
+    finally:
+        shutil.rmtree(top, ignore_errors=True)
 
 
 if __name__ == "__main__":

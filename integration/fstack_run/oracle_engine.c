@@ -10,7 +10,10 @@
  * results are written back into the request's segments, at that poll, only
  * for etype 0.  oracle_engine_fail() plays a GPU failure as the engine
  * reports it: staged requests complete with ESPGPU_EIO and untouched
- * buffers, process() answers ESPGPU_EIO, the probe ENXIO.
+ * buffers, process() answers ESPGPU_EIO, the probe ENXIO.  AH sessions
+ * (CSP_MODE_DIGEST) are offered, as by the shim, only with FF_GPUCRYPTO_AH=1
+ * in the environment; their requests are swcr_authcompute's, served with
+ * oref_hmac.
  */
 #include <stdint.h>
 #include <stdlib.h>
@@ -40,10 +43,17 @@ static struct oe_pend {
 	uint8_t *rec;                 /* the processed record (malloc'ed) */
 	uint32_t rec0, wb_off, wb_len;  /* write-back: [wb_off, wb_off + wb_len) of the record */
 } g_pend[OE_MAX_PENDING];
-static int g_npend, g_ready, g_failed;
+static int g_npend, g_ready, g_failed, g_ah;
 
 int  ff_gpucrypto_host_ready(void) { return (g_ready); }
-void oracle_engine_init(void) { g_ready = 1; }
+void
+oracle_engine_init(void)
+{
+	const char *ah = getenv("FF_GPUCRYPTO_AH");     /* as ff_gpucrypto_host_init_proc */
+
+	g_ah = ah != NULL && atoi(ah) > 0;
+	g_ready = 1;
+}
 int  ff_gpucrypto_host_failed(void) { return (g_failed); }
 void oracle_engine_fail(void) { g_failed = 1; }
 
@@ -54,6 +64,8 @@ ff_gpucrypto_host_probe(const struct espgpu_session_params *csp)
 
 	if (g_failed)
 		return (ESPGPU_ENXIO);
+	if (csp->csp_mode == ESPGPU_CSP_MODE_DIGEST && !g_ah)
+		return (ESPGPU_EINVAL);
 	r = espgpu_probesession(csp);
 	if (r != ESPGPU_PROBE_HARDWARE)
 		return (r);
@@ -125,6 +137,48 @@ seg_io(const struct espgpu_seg *segs, int nsegs, uint32_t off, uint8_t *p, uint3
 
 static uint32_t be32(const uint8_t *p) { return ((uint32_t)p[0] << 24 | p[1] << 16 | p[2] << 8 | p[3]); }
 
+/* An AH session's request: the digest of [crp_payload_start, +length) as it
+ * stands, then crp_esn for ESN sessions (swcr_authcompute); COMPUTE writes
+ * the first mlen bytes at crp_digest_start, VERIFY compares them. */
+static int
+oe_digest(const struct oe_ses *s, const struct espgpu_req *r)
+{
+	int hl = s->aalg == ESPGPU_CRYPTO_SHA1_HMAC ? 20 : s->aalg == ESPGPU_CRYPTO_SHA2_256_HMAC ? 32 :
+	    s->aalg == ESPGPU_CRYPTO_SHA2_384_HMAC ? 48 : 64;
+	int mlen = s->mlen ? s->mlen : hl, esn = (s->flags & ESPGPU_CSP_F_ESN) != 0;
+	int plen = r->crp_payload_length, doff = r->crp_digest_start - r->crp_payload_start;
+	struct oe_pend *p = &g_pend[g_npend++];
+	uint8_t dg[64], *msg;
+
+	p->opaque = r->opaque;
+	memcpy(p->segs, r->segs, (size_t)r->nsegs * sizeof(r->segs[0]));
+	p->nsegs = r->nsegs;
+	p->rec = NULL;
+	p->wb_len = 0;
+	if (r->crp_aad != NULL || r->crp_aad_length != 0 || (r->crp_op & ESPGPU_CRYPTO_OP_ENCRYPT) ||
+	    plen < 1 || plen > 65535 || doff < 0 || (doff & 3) || doff + mlen > plen) {
+		p->etype = ESPGPU_EINVAL;
+		return (ESPGPU_OK);
+	}
+	msg = malloc((size_t)plen + 4);
+	seg_io(r->segs, r->nsegs, (uint32_t)r->crp_payload_start, msg, (uint32_t)plen, 1);
+	if (esn)
+		memcpy(msg + plen, r->crp_esn, 4);
+	oref_hmac(s->aalg, s->akey, s->aklen, msg, (size_t)plen + (esn ? 4 : 0), dg);
+	if (r->crp_op & ESPGPU_CRYPTO_OP_VERIFY_DIGEST) {
+		p->etype = memcmp(dg, msg + doff, (size_t)mlen) == 0 ? ESPGPU_OK : ESPGPU_EBADMSG;
+		free(msg);
+		return (ESPGPU_OK);
+	}
+	memcpy(msg, dg, (size_t)mlen);                      /* written back at the poll */
+	p->etype = ESPGPU_OK;
+	p->rec = msg;
+	p->rec0 = (uint32_t)r->crp_digest_start;
+	p->wb_off = 0;
+	p->wb_len = (uint32_t)mlen;
+	return (ESPGPU_OK);
+}
+
 int
 ff_gpucrypto_host_process(const struct espgpu_req *r, int hint)
 {
@@ -141,6 +195,8 @@ ff_gpucrypto_host_process(const struct espgpu_req *r, int hint)
 	if (g_npend == OE_MAX_PENDING || r->nsegs > 16)
 		return (ESPGPU_ERESTART);
 	s = &g_ses[r->session];
+	if (s->mode == ESPGPU_CSP_MODE_DIGEST)
+		return (oe_digest(s, r));
 	gcm = s->mode == ESPGPU_CSP_MODE_AEAD;
 	ctr = s->calg == ESPGPU_CRYPTO_AES_ICM;
 	null = s->calg == ESPGPU_CRYPTO_NULL_CBC;
@@ -190,7 +246,7 @@ ff_gpucrypto_poll(void)
 		struct oe_pend *p = &g_pend[i];
 		if (g_failed)
 			p->etype = ESPGPU_EIO;
-		if (p->etype == ESPGPU_OK)
+		if (p->etype == ESPGPU_OK && p->wb_len)
 			seg_io(p->segs, p->nsegs, p->rec0 + p->wb_off, p->rec + p->wb_off, p->wb_len, 0);
 		free(p->rec);
 		ff_gpucrypto_done(p->opaque, p->etype);
