@@ -215,6 +215,9 @@ struct espgpu_ctx {
   uint32_t *d_work = nullptr, *d_order = nullptr, *d_nchunks = nullptr;
   Chunk *d_chunks = nullptr;
   uint32_t max_chunks = 0;
+  // espgpu_replay_update_batch's workspace, grown to the largest (n, nreplay) seen
+  void *d_replay_ws = nullptr;
+  uint32_t replay_ws_n = 0, replay_ws_sas = 0;
   // staging
   std::vector<Slot> slots;
   int cur = 0;
@@ -958,6 +961,7 @@ void espgpu_fini(espgpu_ctx *c) {
   hipFree(c->d_queue);
   hipFree(c->d_ej0);
   hipFree(c->d_work); hipFree(c->d_order); hipFree(c->d_chunks); hipFree(c->d_nchunks);
+  hipFree(c->d_replay_ws);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
   if (c->ev_last) hipEventDestroy(c->ev_last);
@@ -1869,6 +1873,38 @@ int espgpu_replay_update(espgpu_replay *r, uint32_t *bitmap, uint32_t seq) {
   return 0;
 }
 
+// The same update on the 64-bit sequence number the record was authenticated
+// under (ESN: esn_hi << 32 | seq; else seq): nothing is inferred, so a record
+// that has fallen below the window is refused, never taken for the next
+// subspace.  The rule espgpu_replay_update_batch applies (replay.hip).
+int espgpu_replay_update64(espgpu_replay *r, uint32_t *bitmap, uint64_t seq64) {
+  if (!r || (r->wsize && !bitmap)) return ESPGPU_EINVAL;
+  if (r->wsize == 0) return 0;
+  const uint64_t window = (uint64_t)r->wsize << 3;
+  // as espgpu_replay_update, and the redundant block (key.c:3343-3351): a
+  // ring of at least window + 32 bits, or two sequence numbers of one window
+  // span could share a bit
+  if (!espgpu_replay_params_ok(r) || (uint64_t)r->bitmap_size * 32 < window + 32) return ESPGPU_EINVAL;
+  const uint64_t s = (r->flags & ESPGPU_REPLAY_ESN) ? seq64 : (uint32_t)seq64, top = r->last;
+  if (s == 0 && top == 0) return ESPGPU_EACCES;
+  uint32_t *bm = bitmap + r->bitmap_off;
+  const uint64_t mask = r->bitmap_size - 1;
+  uint32_t &word = bm[(s >> 5) & mask];
+  const uint32_t bit = 1u << (s & 31);
+  if (s > top) {
+    uint64_t diff = (s >> 5) - (top >> 5);          // clear the words the top moves past
+    if (diff > r->bitmap_size) diff = r->bitmap_size;
+    for (uint64_t k = 0; k < diff; ++k) bm[(k + (top >> 5) + 1) & mask] = 0;
+    word |= bit;
+    r->last = s;
+    return 0;
+  }
+  if (top - s >= window) return ESPGPU_EACCES;      // below the window
+  if (word & bit) return ESPGPU_EACCES;
+  word |= bit;
+  return 0;
+}
+
 int espgpu_get_stats(espgpu_ctx *c, espgpu_stats *st) {
   if (!c || !st) return ESPGPU_EINVAL;
   *st = c->stats;
@@ -1882,6 +1918,55 @@ int espgpu_get_stats(espgpu_ctx *c, espgpu_stats *st) {
 static int batch_rc(espgpu_ctx *c, int e) {
   if (e == ESPGPU_EIO && !c->failed) ctx_fail(c, "batch launch failed");
   return e;
+}
+
+// The workspace grows with n and nreplay and is kept.  An allocation that
+// fails is ENOMEM with nothing launched and the ctx healthy.
+static int ensure_replay_ws(espgpu_ctx *c, uint32_t n, uint32_t nreplay) {
+  if (c->d_replay_ws && n <= c->replay_ws_n && nreplay <= c->replay_ws_sas) return 0;
+  const uint32_t cap_n = std::max({n, c->replay_ws_n, 1024u}), cap_sas = std::max(nreplay, c->replay_ws_sas);
+  hipFree(c->d_replay_ws);               // (waits for the launches that use it)
+  c->d_replay_ws = nullptr;
+  c->replay_ws_n = c->replay_ws_sas = 0;
+  const size_t bytes = replay_update_workspace_bytes(cap_n, cap_sas);
+  if (hipMalloc(&c->d_replay_ws, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    c->d_replay_ws = nullptr;
+    return fail(c, ESPGPU_ENOMEM, "replay update workspace: %zu bytes of device memory not available", bytes);
+  }
+  c->replay_ws_n = cap_n;
+  c->replay_ws_sas = cap_sas;
+  return 0;
+}
+
+static int replay_update_run(espgpu_ctx *c, const uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n,
+                             const uint8_t *d_status, espgpu_replay *d_replay, uint32_t nreplay,
+                             uint32_t *d_bitmap, uint8_t *d_ustatus, hipStream_t st) {
+  if (c->fault & ESPGPU_FAULT_LAUNCH) {
+    c->fault &= ~(uint32_t)ESPGPU_FAULT_LAUNCH;
+    return fail(c, ESPGPU_EIO, "injected launch failure");
+  }
+  // the workspace is per ctx, as the planner's: stream-ordered after the last launch
+  if (c->launched && st != c->last_st) HIPCHK(c, hipStreamWaitEvent(st, c->ev_last, 0));
+  if (launch_replay_update(d_arena, d_desc, n, d_status, d_replay, nreplay, d_bitmap, d_ustatus, c->d_replay_ws, st))
+    return fail(c, ESPGPU_EIO, "replay update launch failed");
+  HIPCHK(c, hipEventRecord(c->ev_last, st));
+  c->last_st = st;
+  c->launched = true;
+  return 0;
+}
+
+int espgpu_replay_update_batch(espgpu_ctx *c, const uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n,
+                               const uint8_t *d_status, espgpu_replay *d_replay, uint32_t nreplay,
+                               uint32_t *d_bitmap, uint8_t *d_ustatus, void *stream) {
+  if (!c || (n && (!d_arena || !d_desc || !d_status || !d_ustatus || (nreplay && (!d_replay || !d_bitmap)))))
+    return ESPGPU_EINVAL;
+  if (c->failed) return ESPGPU_EIO;
+  if (n == 0) return 0;
+  int e = ensure_replay_ws(c, n, nreplay);
+  if (e) return e;
+  return batch_rc(c, replay_update_run(c, d_arena, d_desc, n, d_status, d_replay, nreplay, d_bitmap, d_ustatus,
+                                       reinterpret_cast<hipStream_t>(stream)));
 }
 
 int espgpu_decrypt_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n,

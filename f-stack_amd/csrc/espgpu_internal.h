@@ -1,6 +1,6 @@
 // espgpu_internal.h — device-side data layouts shared by the host runtime
 // (espgpu.cpp) and the HIP kernels (esp_gcm.hip, esp_cbc.hip, esp_ah.hip,
-// plan.hip, xfer.hip).
+// plan.hip, replay.hip, xfer.hip).
 #pragma once
 #include <stdint.h>
 
@@ -236,6 +236,14 @@ int launch_eta(const EtaParams &p, int encrypt, int kinds, int grid, void *strea
 int launch_digest(const DigestParams &p, int narrow, int wide, int grid, void *stream);
 int launch_replay_check(const uint8_t *arena, espgpu_desc *desc, uint32_t n, const espgpu_replay *rp,
                         uint32_t nrp, const uint32_t *bitmap, uint8_t *rstatus, void *stream);
+// The window update of a batch (replay.hip): ws = replay_update_workspace_bytes(n, nrp)
+// bytes of device memory (monotonic in both), free again once the launches
+// have run.  kReplayScanBlock: grouped positions per workgroup of its max-scan.
+constexpr uint32_t kReplayScanBlock = 1024;
+size_t replay_update_workspace_bytes(uint32_t n, uint32_t nrp);
+int launch_replay_update(const uint8_t *arena, const espgpu_desc *desc, uint32_t n, const uint8_t *status,
+                         espgpu_replay *rp, uint32_t nrp, uint32_t *bitmap, uint8_t *ustatus, void *ws,
+                         void *stream);
 int launch_xfer(const XferSpan *spans, uint32_t nspans, const uint8_t *status, void *stream);
 int launch_replay_merge(uint8_t *status, const uint8_t *rstatus, uint32_t n, void *stream);
 int launch_plan(const espgpu_desc *d_desc, uint32_t n, const DevSA *sas, uint32_t nsas, uint32_t cap_sas,

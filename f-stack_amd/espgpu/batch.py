@@ -105,6 +105,22 @@ def replay_check(driver, arena, desc, n, replay, bitmap, rstatus, stream=None):
         raise RuntimeError("espgpu_replay_check_batch: %s" % driver.last_error())
 
 
+def replay_update(driver, arena, desc, n, status, replay, bitmap, ustatus, stream=None):
+    """Window update after decrypt (espgpu_replay_update_batch): the records
+    with status 0 update their SA's window in replay / bitmap (both stay on the
+    device for the next batch) as espgpu_replay_update64 would one by one in
+    index order; ustatus receives 0 / EACCES (EINVAL for an unusable window)
+    per record, for replay_merge."""
+    for t in (arena, desc, status, replay, bitmap, ustatus):
+        assert t.is_cuda and t.is_contiguous()
+    nrep = replay.numel() // REPLAY_DTYPE.itemsize
+    rc = driver.lib.espgpu_replay_update_batch(
+        driver.ctx, arena.data_ptr(), desc.data_ptr(), n, status.data_ptr(), replay.data_ptr(), nrep,
+        bitmap.data_ptr(), ustatus.data_ptr(), _stream_ptr(stream))
+    if rc:
+        raise RuntimeError("espgpu_replay_update_batch: %s (%d)" % (driver.last_error(), rc))
+
+
 def replay_merge(driver, status, rstatus, n, stream=None):
     rc = driver.lib.espgpu_replay_merge(driver.ctx, status.data_ptr(), rstatus.data_ptr(), n,
                                         _stream_ptr(stream))

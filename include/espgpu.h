@@ -355,7 +355,16 @@ int  espgpu_decrypt_host(espgpu_ctx *ctx, const uint8_t *h_arena, uint64_t arena
  * netipsec/keydb.h:206-213): `last` = ESN high << 32 | low of the window
  * top, `wsize` in bytes (window = wsize * 8 packets, 0 = no replay check),
  * `bitmap_size` u32 words (a power of two, key.c:3346-3351) starting at word
- * `bitmap_off` of a shared bitmap array. */
+ * `bitmap_off` of a shared bitmap array.
+ *
+ * The inbound sequence on a device-resident batch, windows and bitmaps in
+ * device memory from one batch to the next, all on one stream:
+ *   1. espgpu_replay_check_batch   ipsec_chkreplay; fills desc.esn_hi
+ *   2. espgpu_decrypt_batch        ICV check, decrypt (trailer checks)
+ *   3. espgpu_replay_update_batch  ipsec_updatereplay for what authenticated
+ *   4. espgpu_replay_merge, once with 1's and once with 3's result.
+ * espgpu_replay_update / _update64 are the same update on the host, one
+ * record per call. */
 #define ESPGPU_REPLAY_ESN    0x1     /* SADB_X_SAFLAGS_ESN  */
 #define ESPGPU_REPLAY_CYCSEQ 0x2     /* SADB_X_EXT_CYCSEQ   */
 #define ESPGPU_EACCES        13      /* replayed (esp_input's EACCES, esps_replay) */
@@ -389,6 +398,47 @@ int  espgpu_replay_merge(espgpu_ctx *ctx, uint8_t *d_status, const uint8_t *d_rs
 /* Host: ipsec_updatereplay (ipsec.c:1338-1436) for one authenticated record,
  * in arrival order per SA: 0 (window advanced / bit set) or ESPGPU_EACCES. */
 int  espgpu_replay_update(struct espgpu_replay *r, uint32_t *bitmap, uint32_t seq);
+/* Host: the same update on the 64-bit sequence number the record was
+ * authenticated under: seq64 = esn_hi << 32 | seq for an ESN window, seq for
+ * any other (the high word is ignored).  With T = r->last, W = wsize * 8:
+ *   wsize == 0                         0
+ *   !espgpu_replay_params_ok(r), or no redundant block
+ *   (bitmap_size * 32 < W + 32; key.c:3343-3351 always allocates one)
+ *                                      ESPGPU_EINVAL, nothing touched
+ *   seq64 == 0 && T == 0               ESPGPU_EACCES
+ *   seq64 > T                          advance, set the bit, last = seq64: 0
+ *   seq64 + W > T (in the window)      ESPGPU_EACCES if its bit is set, else set it: 0
+ *   otherwise (below the window)       ESPGPU_EACCES, nothing changes.
+ * This is ipsec_updatereplay(seq) whenever seq64 is what that function infers
+ * from seq (the value congruent to seq in [T-W+1, T-W+2^32]; for a non-ESN SA
+ * with the high word unchanged), which holds for every record that passed
+ * ipsec_chkreplay against the window of the moment.  The one deliberate
+ * difference: an ESN record that was authenticated under high word h and has
+ * fallen below the window since (earlier records of its batch moved the top)
+ * is ESPGPU_EACCES here.  ipsec_updatereplay would infer h + 1 for it and
+ * move the window by about 2^32, under a high word its ICV was never checked
+ * with. */
+int  espgpu_replay_update64(struct espgpu_replay *r, uint32_t *bitmap, uint64_t seq64);
+/* esp_input_cb's window update for a device-resident batch, after
+ * espgpu_decrypt_batch.  Record i takes part if d_status[i] == 0 (it
+ * authenticated), d_desc[i].sa < nreplay, its len >= 8 and its window has
+ * wsize != 0; seq is read big-endian at byte 4 of the record and esn_hi from
+ * the descriptor, where espgpu_replay_check_batch put it.  d_ustatus[i] is
+ * what espgpu_replay_update64 returns when applied to each SA's taking-part
+ * records one after another in index (arrival) order, starting from
+ * d_replay[sa] and d_bitmap as they stand; 0 for records that take no part.
+ * When the work completes, every d_replay[sa].last and every window's bitmap
+ * words equal that sequential run's; words outside the windows are untouched.
+ * The records of a window with unusable parameters get ESPGPU_EINVAL and the
+ * window is not touched.  espgpu_replay_merge(d_status, d_ustatus, n) folds
+ * the result in.  Asynchronous, no host round trip; stream-ordered on the
+ * ctx like the other batch entries (the workspace belongs to the ctx and
+ * grows with n and nreplay: ESPGPU_ENOMEM, with nothing launched and the ctx
+ * healthy, if it cannot be allocated). */
+int  espgpu_replay_update_batch(espgpu_ctx *ctx, const uint8_t *d_arena,
+                                const struct espgpu_desc *d_desc, uint32_t n, const uint8_t *d_status,
+                                struct espgpu_replay *d_replay, uint32_t nreplay, uint32_t *d_bitmap,
+                                uint8_t *d_ustatus, void *stream);
 
 /* Device time of the last timed batch's crypto kernels (ms, from HIP events
  * on the batch stream).  Process-path batches of <= 128 KiB (a burst on its
