@@ -16,6 +16,7 @@ from test_replay_update64 import _seqs, _windows
 EACCES, EINVAL = 13, 22
 GUARD = 0xDEADBEEF
 SCAN_BLOCK = 1024          # grouped positions per workgroup of the max-scan (kReplayScanBlock)
+SORT_TILE = 2048           # records per workgroup of a radix pass (replay.hip kSortTile)
 DESC = np.dtype([("off4", "<u4"), ("len", "<u2"), ("sa", "<u2"), ("esn_hi", "<u4"), ("salt", "<u4")])
 
 
@@ -91,11 +92,13 @@ def _host_run(tab, words, desc, seq32, status):
     return ust, tab, words
 
 
-def _device_run(drv, tab, words, arena, desc, status, calls=None):
-    """Upload, run replay_update (once, or per (start, count) slice of
-    `calls` back to back without a sync), download."""
+def _device_run(drv, tab, words, arena, desc, status, calls=None, stream=None):
+    """Upload, run replay_update (once, or per (start, count) or (start,
+    count, nreplay) slice of `calls` back to back without a sync; nreplay
+    passes only the table's first entries), download.  With `stream`, the
+    calls go to that stream once it has waited for the uploads."""
     torch = _torch()
-    from espgpu.batch import replay_update
+    from espgpu.batch import replay_update, REPLAY_DTYPE
     n = len(desc)
     d_arena = torch.from_numpy(arena).cuda()
     d_desc = torch.from_numpy(desc.view(np.uint8).copy()).cuda()
@@ -103,9 +106,15 @@ def _device_run(drv, tab, words, arena, desc, status, calls=None):
     d_tab = torch.from_numpy(tab.view(np.uint8).copy()).cuda()
     d_words = torch.from_numpy(words.view(np.int32).copy()).cuda()
     d_ust = torch.full((max(n, 1),), 0x77, dtype=torch.uint8, device="cuda")
-    for a, cnt in (calls or [(0, n)]):
-        replay_update(drv, d_arena, d_desc[a * 16:], cnt, d_status[a:], d_tab, d_words, d_ust[a:])
-    torch.cuda.synchronize()
+    if stream is not None:
+        stream.wait_stream(torch.cuda.current_stream())
+    for a, cnt, *nrp in (calls or [(0, n)]):
+        rtab = d_tab[:nrp[0] * REPLAY_DTYPE.itemsize] if nrp else d_tab
+        replay_update(drv, d_arena, d_desc[a * 16:], cnt, d_status[a:], rtab, d_words, d_ust[a:], stream=stream)
+    if stream is not None:
+        stream.synchronize()
+    else:
+        torch.cuda.synchronize()
     assert np.array_equal(d_desc.cpu().numpy(), desc.view(np.uint8)), "d_desc modified"
     assert np.array_equal(d_status.cpu().numpy(), status), "d_status modified"
     return (d_ust.cpu().numpy()[:n], d_tab.cpu().numpy().view(tab.dtype),
