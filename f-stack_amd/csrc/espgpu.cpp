@@ -1969,6 +1969,74 @@ int espgpu_replay_update_batch(espgpu_ctx *c, const uint8_t *d_arena, const espg
                                        reinterpret_cast<hipStream_t>(stream)));
 }
 
+// ---- outbound framing ----------------------------------------------------------
+// The shape from session parameters, through the fields newsession keeps in
+// DevSA (mode, calg, mlen), so the host rule and the kernels read one table.
+int espgpu_esp_frame_shape(const espgpu_session_params *csp, uint32_t flags, espgpu_eshape *shape) {
+  if (!csp || !shape || probe_caps(csp) >= 0) return ESPGPU_EINVAL;
+  uint32_t mode = (uint32_t)csp->csp_mode, mlen = (uint32_t)csp->csp_auth_mlen;
+  if (csp->csp_mode == ESPGPU_CSP_MODE_AEAD) {
+    if (!mlen) mlen = 16;
+  } else if (csp->csp_mode == ESPGPU_CSP_MODE_ETA) {
+    if (!mlen)                                     // the whole hash (swcr_setup_auth)
+      mlen = csp->csp_auth_alg == ESPGPU_CRYPTO_SHA2_256_HMAC ? 32u
+           : csp->csp_auth_alg == ESPGPU_CRYPTO_SHA2_384_HMAC ? 48u
+           : csp->csp_auth_alg == ESPGPU_CRYPTO_SHA2_512_HMAC ? 64u : 20u;
+  } else if (csp->csp_mode == ESPGPU_CSP_MODE_CIPHER) {
+    mode = ESPGPU_CSP_MODE_ETA;                    // as newsession files it
+    mlen = 0;
+  }
+  espgpu_eshape s;
+  if (!esp_shape_of(mode, (uint32_t)csp->csp_cipher_alg, mlen, flags, &s)) return ESPGPU_EINVAL;
+  *shape = s;
+  return 0;
+}
+
+// esp_output between m_makespace and crypto_dispatch (xform_esp.c:703-716,
+// :782-887) for one record.  The rule espgpu_esp_frame_batch applies (replay.hip).
+int espgpu_esp_frame(espgpu_outsa *o, const espgpu_eshape *s, uint8_t *rec, uint32_t len, uint32_t rlen,
+                     uint8_t next_header, uint32_t *esn_hi) {
+  if (!o || !s || !rec || !esn_hi) return ESPGPU_EINVAL;
+  if ((s->ivlen != 0 && s->ivlen != 8 && s->ivlen != 16) || (s->blks != 4 && s->blks != 16)) return ESPGPU_EINVAL;
+  if (rlen > 0xffffu || 8 + s->ivlen + rlen + esp_padding(rlen, s->blks) + s->alen != len) return ESPGPU_EINVAL;
+  if (esp_out_room(o->count, o->flags) == 0) return ESPGPU_EINVAL;
+  o->count++;                                                    // :793
+  const uint64_t cntr = o->cntr;
+  if (s->ivlen == 8) o->cntr++;                                  // :802-803
+  esp_frame_write(rec, *s, o->flags, o->spi, o->count, cntr, rlen, next_header);
+  *esn_hi = (o->flags & ESPGPU_OUT_ESN) ? (uint32_t)(o->count >> 32) : 0u;   // :799
+  return 0;
+}
+
+static int esp_frame_run(espgpu_ctx *c, uint8_t *d_arena, espgpu_desc *d_desc, const uint32_t *d_frame, uint32_t n,
+                         espgpu_outsa *d_out, uint32_t nout, uint8_t *d_fstatus, hipStream_t st) {
+  if (c->fault & ESPGPU_FAULT_LAUNCH) {
+    c->fault &= ~(uint32_t)ESPGPU_FAULT_LAUNCH;
+    return fail(c, ESPGPU_EIO, "injected launch failure");
+  }
+  // the workspace is per ctx: stream-ordered after the last launch
+  if (c->launched && st != c->last_st) HIPCHK(c, hipStreamWaitEvent(st, c->ev_last, 0));
+  if (launch_esp_frame(d_arena, d_desc, d_frame, n, d_out, nout, c->d_sas, c->cfg.max_sessions, d_fstatus,
+                       c->d_replay_ws, st))
+    return fail(c, ESPGPU_EIO, "esp frame launch failed");
+  HIPCHK(c, hipEventRecord(c->ev_last, st));
+  c->last_st = st;
+  c->launched = true;
+  return 0;
+}
+
+int espgpu_esp_frame_batch(espgpu_ctx *c, uint8_t *d_arena, espgpu_desc *d_desc, const uint32_t *d_frame,
+                           uint32_t n, espgpu_outsa *d_out, uint32_t nout, uint8_t *d_fstatus, void *stream) {
+  if (!c || (n && (!d_arena || !d_desc || !d_frame || !d_fstatus || (nout && !d_out)))) return ESPGPU_EINVAL;
+  if (c->failed) return ESPGPU_EIO;
+  if (n == 0) return 0;
+  // the replay update's workspace holds this one's too (esp_frame_workspace_bytes)
+  int e = ensure_replay_ws(c, n, nout);
+  if (e) return e;
+  return batch_rc(c, esp_frame_run(c, d_arena, d_desc, d_frame, n, d_out, nout, d_fstatus,
+                                   reinterpret_cast<hipStream_t>(stream)));
+}
+
 int espgpu_decrypt_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n,
                          uint8_t *d_status, uint8_t *d_out, uint32_t flags, void *stream) {
   if (!c || (!d_arena && n) || (!d_desc && n) || (!d_status && n)) return ESPGPU_EINVAL;

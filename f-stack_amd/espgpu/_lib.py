@@ -86,6 +86,21 @@ class Replay(C.Structure):
 REPLAY_ESN, REPLAY_CYCSEQ, EACCES = 0x1, 0x2, 13
 
 
+class OutSA(C.Structure):
+    """struct espgpu_outsa: one SA's outbound counters (esp_output, xform_esp.c:782-804)."""
+    _fields_ = [("count", C.c_uint64), ("cntr", C.c_uint64), ("spi", C.c_uint32), ("salt", C.c_uint32),
+                ("flags", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+class EShape(C.Structure):
+    """struct espgpu_eshape: esp_output's hlen - 8, blks and alen."""
+    _fields_ = [("ivlen", C.c_uint32), ("blks", C.c_uint32), ("alen", C.c_uint32)]
+
+
+OUT_ESN, OUT_CYCSEQ, OUT_WRAPCHECK, OUT_CTRCOMPAT = 0x01, 0x02, 0x04, 0x08
+OUT_PAD_SEQ, OUT_PAD_ZERO, OUT_PAD_RAND = 0x10, 0x20, 0x40
+
+
 class Config(C.Structure):
     _fields_ = [("device", C.c_int), ("max_sessions", C.c_uint32),
                 ("batch_records", C.c_uint32), ("batch_bytes", C.c_uint32),
@@ -152,6 +167,10 @@ def lib():
         L.espgpu_replay_params_ok.argtypes = [C.POINTER(Replay)]
         L.espgpu_replay_update64.argtypes = [C.POINTER(Replay), C.POINTER(C.c_uint32), C.c_uint64]
         L.espgpu_replay_update_batch.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp, vp]
+        L.espgpu_esp_frame_shape.argtypes = [C.POINTER(SessionParams), C.c_uint32, C.POINTER(EShape)]
+        L.espgpu_esp_frame.argtypes = [C.POINTER(OutSA), C.POINTER(EShape), vp, C.c_uint32, C.c_uint32,
+                                       C.c_uint8, C.POINTER(C.c_uint32)]
+        L.espgpu_esp_frame_batch.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
         L.espgpu_last_kernel_ms.argtypes = [vp]
         L.espgpu_last_kernel_ms.restype = C.c_float
         L.espgpu_set_tuning.argtypes = [vp, C.c_char_p, C.c_int]

@@ -121,6 +121,30 @@ def replay_update(driver, arena, desc, n, status, replay, bitmap, ustatus, strea
         raise RuntimeError("espgpu_replay_update_batch: %s (%d)" % (driver.last_error(), rc))
 
 
+OUTSA_DTYPE = np.dtype([("count", "<u8"), ("cntr", "<u8"), ("spi", "<u4"), ("salt", "<u4"),
+                        ("flags", "<u4"), ("pad_", "<u4")])
+assert OUTSA_DTYPE.itemsize == 32
+
+
+def esp_frame(driver, arena, desc, frame, n, outsa, fstatus, stream=None):
+    """Outbound framing before encrypt_batch (espgpu_esp_frame_batch): outsa
+    is a uint8 CUDA tensor of OUTSA_DTYPE records indexed by session id (it
+    stays on the device for the next batch), frame an int32 CUDA tensor of n
+    words, rlen | next header << 16.  Each SA's records get their sequence
+    numbers and counter IVs in index order, the padding and the trailer; desc
+    is updated in place (esn_hi, salt; len 0 for refused records) and fstatus
+    receives 0 / EINVAL per record, for replay_merge after the encrypt."""
+    for t in (arena, desc, frame, outsa, fstatus):
+        assert t.is_cuda and t.is_contiguous()
+    assert frame.element_size() == 4 and frame.numel() >= n
+    nout = outsa.numel() // OUTSA_DTYPE.itemsize
+    rc = driver.lib.espgpu_esp_frame_batch(
+        driver.ctx, arena.data_ptr(), desc.data_ptr(), frame.data_ptr(), n, outsa.data_ptr(), nout,
+        fstatus.data_ptr(), _stream_ptr(stream))
+    if rc:
+        raise RuntimeError("espgpu_esp_frame_batch: %s (%d)" % (driver.last_error(), rc))
+
+
 def replay_merge(driver, status, rstatus, n, stream=None):
     rc = driver.lib.espgpu_replay_merge(driver.ctx, status.data_ptr(), rstatus.data_ptr(), n,
                                         _stream_ptr(stream))

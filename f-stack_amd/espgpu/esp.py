@@ -202,6 +202,78 @@ def esp_pad(inner, blocksize=4, next_header=4):
     return bytes(inner) + pad
 
 
+class OutState:
+    """The outbound part of struct secasvar that esp_output advances under the
+    SA lock: replay->count, cntr, and the SA's flags as L.OUT_* bits."""
+
+    def __init__(self, count=0, cntr=0, flags=0):
+        self.count, self.cntr, self.flags = count, cntr, flags
+
+    def copy(self):
+        return OutState(self.count, self.cntr, self.flags)
+
+
+def esp_out_blks(sa, flags=0):
+    """blks = MAX(4, blocksize), native_blocksize (16) for an AES-CTR SA under
+    V_esp_ctr_compatibility (xform_esp.c:710-713)."""
+    return 16 if sa.ctr and flags & L.OUT_CTRCOMPAT else max(4, sa.blocksize)
+
+
+def esp_output_frame(sa_state, sa, payload, next_header, fill=0):
+    """esp_output between m_makespace and crypto_dispatch (xform_esp.c:700-716,
+    782-843, 867-887): returns (record, esn_hi, advanced state).  The record
+    is SPI | sequence number | IV | payload | padding | pad length | next
+    header | ICV field; what esp_output leaves to others -- a CBC SA's IV
+    (arc4rand), the pad bytes without PAD_SEQ / PAD_ZERO, the ICV field -- is
+    `fill`.  With OUT_WRAPCHECK the end of the number space is ah_output's
+    (xform_ah.c:940-950): (None, None, sa_state unchanged)."""
+    st, f = sa_state.copy(), sa_state.flags
+    rlen = len(payload)
+    blks = esp_out_blks(sa, f)
+    padding = ((blks - ((rlen + 2) % blks)) % blks) + 2                        # :716
+    if f & L.OUT_WRAPCHECK and not f & L.OUT_CYCSEQ and (
+            st.count == 2**64 - 1 or (not f & L.OUT_ESN and st.count & 0xffffffff == 0xffffffff)):
+        return None, None, sa_state
+    st.count = (st.count + 1) & (2**64 - 1)                                    # :793
+    esn_hi = st.count >> 32 if f & L.OUT_ESN else 0                            # :799
+    hdr = struct.pack(">II", sa.spi, st.count & 0xffffffff)                    # :783-797
+    if sa.alg == GCM or sa.ctr:                                                # :802-803, :869-881
+        iv = struct.pack(">Q", st.cntr)
+        st.cntr = (st.cntr + 1) & (2**64 - 1)
+    else:
+        iv = bytes([fill]) * sa.ivlen                                          # :884, the caller's
+    if f & L.OUT_PAD_SEQ:                                                      # :824-835
+        pad = bytes(range(1, padding - 1))
+    elif f & L.OUT_PAD_ZERO:
+        pad = bytes(padding - 2)
+    else:
+        pad = bytes([fill]) * (padding - 2)
+    pad += bytes([padding - 2, next_header])                                   # :838-839
+    return hdr + iv + bytes(payload) + pad + bytes([fill]) * sa.alen, esn_hi, st
+
+
+def esp_frame_shape(sa, flags=0):
+    """espgpu_esp_frame_shape for the SA's session parameters: an L.EShape."""
+    import ctypes as C
+    p, _keep = sa.csp()._c()
+    shape = L.EShape()
+    rc = L.lib().espgpu_esp_frame_shape(C.byref(p), flags, C.byref(shape))
+    if rc:
+        raise ValueError("espgpu_esp_frame_shape: %d" % rc)
+    return shape
+
+
+def esp_frame_host(outsa, shape, rec, rlen, next_header, esn_hi=0):
+    """espgpu_esp_frame, the engine's host rule, on a bytearray record and an
+    L.OutSA: returns (status, esn_hi), esn_hi as passed in when refused."""
+    import ctypes as C
+    buf = (C.c_uint8 * max(len(rec), 1)).from_buffer(rec) if len(rec) else None
+    hi = C.c_uint32(esn_hi)
+    rc = L.lib().espgpu_esp_frame(C.byref(outsa), C.byref(shape), C.cast(buf, C.c_void_p) if buf else None,
+                                  len(rec), rlen, next_header, C.byref(hi))
+    return rc, hi.value
+
+
 def trailer_word(plain_payload):
     """The 32-bit word the kernels' fused trailer check produces for a
     decrypted payload (espgpu_decrypt_batch_trailer, include/espgpu.h):

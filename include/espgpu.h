@@ -440,6 +440,91 @@ int  espgpu_replay_update_batch(espgpu_ctx *ctx, const uint8_t *d_arena,
                                 struct espgpu_replay *d_replay, uint32_t nreplay, uint32_t *d_bitmap,
                                 uint8_t *d_ustatus, void *stream);
 
+/* ---- outbound framing (what esp_output does between m_makespace and
+ *      crypto_dispatch, freebsd/netipsec/xform_esp.c:703-716, :782-887) ----
+ * One SA's outbound state as esp_output reads and advances it under the SA
+ * lock (struct secasvar / secreplay, netipsec/keydb.h).  The entry at index
+ * `sa` belongs to the session with that id.
+ *
+ * The outbound sequence on a device-resident batch, the per-SA counters in
+ * device memory from one batch to the next, all on one stream:
+ *   1. espgpu_esp_frame_batch   SPI, sequence number, counter IV, padding,
+ *                               trailer; fills desc.esn_hi and desc.salt
+ *   2. espgpu_encrypt_batch     encrypt, ICV
+ *   3. espgpu_replay_merge      with 1's result (d_status, d_fstatus, n).
+ * espgpu_esp_frame is the same rule on the host, one record per call. */
+#define ESPGPU_OUT_ESN       0x01    /* SADB_X_SAFLAGS_ESN: esn_hi = count >> 32 (:799)        */
+#define ESPGPU_OUT_CYCSEQ    0x02    /* SADB_X_EXT_CYCSEQ: the sequence number may cycle       */
+#define ESPGPU_OUT_WRAPCHECK 0x04    /* refuse at the end of the number space, as ah_output
+                                        does (xform_ah.c:940-950); esp_output has no such check */
+#define ESPGPU_OUT_CTRCOMPAT 0x08    /* V_esp_ctr_compatibility (:710-713): an AES-CTR SA
+                                        pads to 16 instead of 4                                */
+#define ESPGPU_OUT_PAD_SEQ   0x10    /* SADB_X_EXT_PSEQ (:831-834): pad bytes 1, 2, 3, ...     */
+#define ESPGPU_OUT_PAD_ZERO  0x20    /* SADB_X_EXT_PZERO (:828-829): pad bytes zero            */
+#define ESPGPU_OUT_PAD_RAND  0x40    /* SADB_X_EXT_PRAND (:825-826): the pad bytes are the
+                                        caller's (random data), as with no pad flag at all;
+                                        PAD_SEQ goes before PAD_ZERO if both are set           */
+struct espgpu_outsa {
+	uint64_t count;         /* sav->replay->count: the last sequence number given out   */
+	uint64_t cntr;          /* sav->cntr: the next explicit IV of a CTR/GCM SA           */
+	uint32_t spi;           /* host order; written big-endian                            */
+	uint32_t salt;          /* as espgpu_desc.salt; copied into it for CTR/GCM SAs       */
+	uint32_t flags;         /* ESPGPU_OUT_*                                              */
+	uint32_t pad_;
+};
+/* esp_output's lengths for one SA: hlen = 8 + ivlen (struct newesp + IV; 8
+ * for CTR/GCM, whose IV is the counter, 16 for CBC, 0 for NULL), blks =
+ * MAX(4, blocksize) (:710-713), alen = xform_ah_authsize (:718). */
+struct espgpu_eshape {
+	uint32_t ivlen, blks, alen;
+};
+/* The shape of an ESP session the engine serves (AEAD; ETA with CBC, CTR or
+ * NULL; CIPHER) under the SA's ESPGPU_OUT_* flags (CTRCOMPAT matters): 0, or
+ * ESPGPU_EINVAL for a DIGEST (AH) session or parameters espgpu_newsession
+ * refuses.  Host-only. */
+int  espgpu_esp_frame_shape(const struct espgpu_session_params *csp, uint32_t flags,
+                            struct espgpu_eshape *shape);
+/* Host: frame one record for SA `o`, in arrival order per SA.  `rec` holds
+ * `len` bytes with the rlen raw payload bytes at rec + hlen; the record takes
+ * part if len == hlen + rlen + padding + alen with padding = ((blks - ((rlen +
+ * 2) % blks)) % blks) + 2 (:716), else ESPGPU_EINVAL with nothing touched.
+ *   Default: esp_output to the letter.  count++ (:793); the SPI goes to byte 0
+ *     and the low 32 bits of count big-endian to byte 4 (:783-797); *esn_hi =
+ *     count >> 32 for an ESN SA, else 0.  No wrap check.
+ *   With WRAPCHECK and without CYCSEQ: if count == ~0, or for a non-ESN SA
+ *     (uint32_t)count == ~0, ESPGPU_EINVAL and nothing is touched: not rec,
+ *     not *o, not *esn_hi.
+ *   CTR/GCM SAs (ivlen 8): cntr++ and its value before that big-endian into
+ *     the 8 IV bytes at byte 8 (:802-803, :869-881); the caller copies o->salt
+ *     into the descriptor.  CBC SAs: the 16 IV bytes are the caller's
+ *     (arc4rand, :884) and stay as they are.
+ *   Padding (:824-835): PAD_SEQ writes 1, 2, 3, ..., PAD_ZERO zeros; otherwise
+ *     the padding - 2 pad bytes stay as they are.  Then pad[padding - 2] =
+ *     padding - 2 and pad[padding - 1] = next_header (:838-839).
+ * The payload, the ICV field and everything outside the record are untouched. */
+int  espgpu_esp_frame(struct espgpu_outsa *o, const struct espgpu_eshape *shape, uint8_t *rec,
+                      uint32_t len, uint32_t rlen, uint8_t next_header, uint32_t *esn_hi);
+/* Frame a device-resident batch for espgpu_encrypt_batch.  d_desc[i] carries
+ * off4, len (the full record) and sa from the caller; d_frame[i] holds rlen
+ * in bits 0-15 and the next header in bits 16-23; d_out[nout] is indexed by
+ * the session id.  The shape is the ctx's own session `sa`'s, so a record
+ * takes part if sa < nout, the session exists and is not a DIGEST one, and
+ * len fits as for espgpu_esp_frame.  The result is espgpu_esp_frame applied
+ * to each SA's taking-part records one after another in index (arrival)
+ * order, starting from d_out[sa] as it stands: the record bytes, d_desc[i].
+ * esn_hi, d_desc[i].salt = d_out[sa].salt for CTR/GCM SAs, d_fstatus[i] = 0,
+ * and the SA's count / cntr when the work completes.  A record that takes no
+ * part or is refused by WRAPCHECK (then so is the rest of its SA's batch)
+ * gets d_fstatus[i] = ESPGPU_EINVAL and d_desc[i].len = 0, so the encrypt
+ * kernels drop it; it consumes no number and nothing else of it is written.
+ * The entries of SAs with no accepted record are untouched.  Asynchronous, no
+ * host round trip; stream-ordered on the ctx like the other batch entries
+ * (it shares espgpu_replay_update_batch's workspace: ESPGPU_ENOMEM, with
+ * nothing launched and the ctx healthy, if that cannot grow). */
+int  espgpu_esp_frame_batch(espgpu_ctx *ctx, uint8_t *d_arena, struct espgpu_desc *d_desc,
+                            const uint32_t *d_frame, uint32_t n, struct espgpu_outsa *d_out,
+                            uint32_t nout, uint8_t *d_fstatus, void *stream);
+
 /* Device time of the last timed batch's crypto kernels (ms, from HIP events
  * on the batch stream).  Process-path batches of <= 128 KiB (a burst on its
  * slot's own stream) are not timed: the two event markers cost a 32-record
