@@ -1,0 +1,187 @@
+// classify.h — the inbound classification rule (include/espgpu.h, the
+// classification block): one function for espgpu_esp_classify on the host and
+// cls_kernel on the device (classify.hip), and espgpu_sad_build's table.
+//
+// Plain C++ with no HIP header, so the host side also builds with the host
+// compiler alone (tools/classify_selftest.cpp runs it under its sanitizers).
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include "espgpu.h"
+
+#if defined(__HIPCC__)
+#define ESPGPU_HD __host__ __device__
+#else
+#define ESPGPU_HD
+#endif
+
+namespace espgpu {
+
+// key_u32hash (key.c:295-299): fnv_32_buf (sys/fnv_hash.h:23-31) over the SPI
+// as struct secasvar stores it, in network byte order.
+ESPGPU_HD inline uint32_t key_u32hash(uint32_t spi) {
+  uint32_t h = 33554467u;                              // FNV1_32_INIT
+  for (int s = 24; s >= 0; s -= 8) h = (h * 0x01000193u) ^ ((spi >> s) & 0xffu);
+  return h;
+}
+
+// A dword of the packet in memory order (byte k in bits 8k..8k+7).  The device
+// reads it whole: the header is 4-byte aligned by off4.  The host takes it
+// byte by byte, from wherever the caller's buffer starts.
+ESPGPU_HD inline uint32_t cls_ld32(const uint8_t *p) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return *reinterpret_cast<const uint32_t *>(p);
+#else
+  return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+#endif
+}
+
+ESPGPU_HD inline uint32_t cls_bswap32(uint32_t x) { return __builtin_bswap32(x); }
+// the big-endian 16-bit field in the low / the high half of a memory-order dword
+ESPGPU_HD inline uint32_t cls_be16lo(uint32_t w) { return ((w & 0xffu) << 8) | ((w >> 8) & 0xffu); }
+ESPGPU_HD inline uint32_t cls_be16hi(uint32_t w) { return ((w >> 8) & 0xff00u) | (w >> 24); }
+
+// The first half of a slot: SPI, sa | proto << 16 | af << 24, salt, flags.  One
+// 16-byte load on the device (the table is 16-byte aligned there).
+struct ClsSlotHead {
+  uint32_t spi, ids, salt, flags;
+};
+static_assert(sizeof(espgpu_sad_entry) == 32 && sizeof(ClsSlotHead) == 16, "SPI table slot layout");
+static_assert(sizeof(espgpu_pkt) == 8 && sizeof(espgpu_desc) == 16, "classification record layouts");
+
+ESPGPU_HD inline ClsSlotHead cls_slot_head(const espgpu_sad_entry *e) {
+  ClsSlotHead h;
+#ifdef __HIP_DEVICE_COMPILE__
+  const uint4 v = *reinterpret_cast<const uint4 *>(e);
+  h.spi = v.x;
+  h.ids = v.y;
+  h.salt = v.z;
+  h.flags = v.w;
+#else
+  h.spi = e->spi;
+  h.ids = (uint32_t)e->sa | (uint32_t)e->proto << 16 | (uint32_t)e->af << 24;
+  h.salt = e->salt;
+  h.flags = e->flags;
+#endif
+  return h;
+}
+
+// Probe from the SPI's home slot to a match or a free slot, at most nslots
+// steps (key_allocsa, key.c:1091-1133: the SPI first, then protocol, family
+// and destination).  dst[] is the packet's destination in memory-order
+// dwords, one for af 4 and four for af 6.  True: *sa and *salt are the entry's.
+ESPGPU_HD inline bool cls_lookup(const espgpu_sad_entry *table, uint32_t nslots, uint32_t spi, uint32_t af,
+                                 const uint32_t dst[4], uint32_t *sa, uint32_t *salt) {
+  if (spi == 0) return false;
+  const uint32_t mask = nslots - 1;
+  uint32_t slot = key_u32hash(spi) & mask;
+  for (uint32_t k = 0; k < nslots; ++k, slot = (slot + 1) & mask) {
+    const ClsSlotHead h = cls_slot_head(table + slot);
+    if (h.spi == 0) return false;
+    if (h.spi != spi) continue;
+    // SPIs are unique in the table: this entry decides
+    if (h.ids >> 16 != (50u | af << 8)) return false;
+    const uint8_t *ed = table[slot].dst;
+    for (uint32_t j = 0; j < (af == 4 ? 1u : 4u); ++j)
+      if (cls_ld32(ed + 4 * j) != dst[j]) return false;
+    *sa = h.ids & 0xffffu;
+    *salt = h.salt;
+    return true;
+  }
+  return false;
+}
+
+// espgpu_esp_classify's rule; *desc is written in every case.  `table` usable
+// (nslots a power of two) is the caller's check.
+ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t nslots, const uint8_t *pkt,
+                                       uint32_t len, uint32_t off4, uint32_t flags, espgpu_desc *desc) {
+  int st = ESPGPU_EINVAL;
+  uint32_t skip = 0, rlen = 0, af = 0, spi = 0, sa = 0, salt = 0, dst[4] = {0, 0, 0, 0};
+  do {
+    if (len < 20) break;
+    // the 20 bytes every packet has, in one round of loads
+    const uint32_t w0 = cls_ld32(pkt), w1 = cls_ld32(pkt + 4), w2 = cls_ld32(pkt + 8), w3 = cls_ld32(pkt + 12),
+                   w4 = cls_ld32(pkt + 16);
+    const uint32_t ver = (w0 >> 4) & 0xfu;
+    if (ver == 4) {                                    // ip_input.c:488-561
+      const uint32_t ihl = w0 & 0xfu, hlen = ihl * 4;
+      if (hlen < 20 || hlen > len) break;
+      if (flags & ESPGPU_CLS_IPCSUM) {
+        // one's-complement sum of the 16-bit words: the same in either byte
+        // order up to a byte swap, and 0xffff is its own swap (in_cksum)
+        uint64_t acc = (uint64_t)w0 + w1 + w2 + w3 + w4;
+        for (uint32_t k = 5; k < ihl; ++k) acc += cls_ld32(pkt + 4 * k);
+        acc = (acc & 0xffffffffu) + (acc >> 32);
+        acc = (acc & 0xffffu) + ((acc >> 16) & 0xffffu) + (acc >> 32);
+        acc = (acc & 0xffffu) + (acc >> 16);
+        acc = (acc & 0xffffu) + (acc >> 16);
+        if (acc != 0xffffu) break;
+      }
+      const uint32_t ip_len = cls_be16hi(w0);
+      if (ip_len < hlen || ip_len > len) break;
+      st = ESPGPU_ENOTSUP;
+      if (cls_be16hi(w1) & 0x3fffu) break;             // IP_MF | IP_OFFMASK, :807
+      if (((w2 >> 8) & 0xffu) != 50) break;            // ip_p
+      st = ESPGPU_EINVAL;
+      if (ip_len - hlen < 8) break;                    // ipsec_input.c:141
+      if (ip_len & 3) break;                           // xform_esp.c:279
+      af = 4;
+      skip = hlen;
+      rlen = ip_len - hlen;
+      dst[0] = w4;
+    } else if (ver == 6) {                             // ip6_input, ipsec6_input
+      if (len < 40) break;
+      const uint32_t plen = cls_be16lo(w1);
+      st = ESPGPU_ENOTSUP;
+      if (plen == 0) break;                            // jumbogram
+      st = ESPGPU_EINVAL;
+      if (40 + plen > len) break;
+      st = ESPGPU_ENOTSUP;
+      if (((w1 >> 16) & 0xffu) != 50) break;           // ip6_nxt
+      for (uint32_t j = 0; j < 4; ++j) dst[j] = cls_ld32(pkt + 24 + 4 * j);
+      if ((dst[0] & 0xc0ffu) == 0x80feu) break;        // fe80::/10
+      st = ESPGPU_EINVAL;
+      if (plen < 8 || (plen & 3)) break;
+      af = 6;
+      skip = 40;
+      rlen = plen;
+    } else {
+      break;
+    }
+    spi = cls_bswap32(cls_ld32(pkt + skip));
+    st = cls_lookup(table, nslots, spi, af, dst, &sa, &salt) ? 0 : ESPGPU_ENOENT;
+  } while (0);
+  espgpu_desc d;
+  d.off4 = st ? off4 : off4 + skip / 4;
+  d.len = st ? (uint16_t)0 : (uint16_t)rlen;
+  d.sa = st ? (uint16_t)0xffffu : (uint16_t)sa;
+  d.esn_hi = 0;
+  d.salt = st ? 0u : salt;
+  *desc = d;
+  return st;
+}
+
+// espgpu_sad_build.
+inline int sad_build(const espgpu_sad_entry *sas, uint32_t nsas, espgpu_sad_entry *table, uint32_t nslots) {
+  if (!table || (nsas && !sas) || nslots == 0 || (nslots & (nslots - 1)) || nslots / 2 < nsas) return ESPGPU_EINVAL;
+  memset(table, 0, (size_t)nslots * sizeof(*table));
+  const uint32_t mask = nslots - 1;
+  for (uint32_t i = 0; i < nsas; ++i) {
+    const espgpu_sad_entry &e = sas[i];
+    if (e.spi == 0 || (e.proto != 50 && e.proto != 51) || (e.af != 4 && e.af != 6) || e.flags != 0)
+      return ESPGPU_EINVAL;
+    if (e.af == 4)
+      for (int k = 4; k < 16; ++k)
+        if (e.dst[k]) return ESPGPU_EINVAL;
+    uint32_t slot = key_u32hash(e.spi) & mask;
+    while (table[slot].spi != 0) {                     // a free slot exists: nslots >= 2 * nsas
+      if (table[slot].spi == e.spi) return ESPGPU_EINVAL;   // key.c:1106-1109
+      slot = (slot + 1) & mask;
+    }
+    table[slot] = e;
+  }
+  return 0;
+}
+
+}  // namespace espgpu

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 
+#include "classify.h"
 #include "espgpu.h"
 #include "espgpu_internal.h"
 #include "fifo_arena.h"
@@ -2035,6 +2036,42 @@ int espgpu_esp_frame_batch(espgpu_ctx *c, uint8_t *d_arena, espgpu_desc *d_desc,
   if (e) return e;
   return batch_rc(c, esp_frame_run(c, d_arena, d_desc, d_frame, n, d_out, nout, d_fstatus,
                                    reinterpret_cast<hipStream_t>(stream)));
+}
+
+// ---- inbound classification ----------------------------------------------------
+int espgpu_sad_build(const espgpu_sad_entry *sas, uint32_t nsas, espgpu_sad_entry *table, uint32_t nslots) {
+  return sad_build(sas, nsas, table, nslots);
+}
+
+// ip_input's header sanity, ipsec_common_input's lookup and esp_input's first
+// checks for one packet.  The rule espgpu_esp_classify_batch applies (classify.h).
+int espgpu_esp_classify(const espgpu_sad_entry *table, uint32_t nslots, const uint8_t *pkt, uint32_t len,
+                        uint32_t off4, uint32_t flags, espgpu_desc *desc) {
+  if (!desc) return ESPGPU_EINVAL;
+  if (!table || nslots == 0 || (nslots & (nslots - 1)) || (!pkt && len) || (flags & ~(uint32_t)ESPGPU_CLS_IPCSUM)) {
+    *desc = espgpu_desc{off4, 0, 0xffff, 0, 0};
+    return ESPGPU_EINVAL;
+  }
+  return esp_classify_rule(table, nslots, pkt, len, off4, flags, desc);
+}
+
+int espgpu_esp_classify_batch(espgpu_ctx *c, const uint8_t *d_arena, const espgpu_pkt *d_pkt, uint32_t n,
+                              const espgpu_sad_entry *d_table, uint32_t nslots, uint32_t flags, espgpu_desc *d_desc,
+                              uint8_t *d_cstatus, void *stream) {
+  if (!c || (flags & ~(uint32_t)ESPGPU_CLS_IPCSUM)) return ESPGPU_EINVAL;
+  if (n && (!d_arena || !d_pkt || !d_table || !d_desc || !d_cstatus || nslots == 0 || (nslots & (nslots - 1)) ||
+            ((uintptr_t)d_arena & 3) || ((uintptr_t)d_table & 15)))
+    return ESPGPU_EINVAL;
+  if (c->failed) return ESPGPU_EIO;
+  if (n == 0) return 0;
+  if (c->fault & ESPGPU_FAULT_LAUNCH) {
+    c->fault &= ~(uint32_t)ESPGPU_FAULT_LAUNCH;
+    return batch_rc(c, fail(c, ESPGPU_EIO, "injected launch failure"));
+  }
+  // no workspace and nothing of the ctx's is touched: the caller's stream orders it
+  if (launch_esp_classify(d_arena, d_pkt, n, d_table, nslots, flags, d_desc, d_cstatus, stream))
+    return batch_rc(c, fail(c, ESPGPU_EIO, "classify kernel launch failed"));
+  return 0;
 }
 
 int espgpu_decrypt_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n,

@@ -1,6 +1,6 @@
 // espgpu_internal.h — device-side data layouts shared by the host runtime
 // (espgpu.cpp) and the HIP kernels (esp_gcm.hip, esp_cbc.hip, esp_ah.hip,
-// plan.hip, replay.hip, xfer.hip).
+// plan.hip, replay.hip, classify.hip, xfer.hip).
 #pragma once
 #include <stdint.h>
 
@@ -321,6 +321,9 @@ __host__ __device__ inline void esp_frame_write(uint8_t *rec, const espgpu_eshap
 size_t esp_frame_workspace_bytes(uint32_t n, uint32_t nout);
 int launch_esp_frame(uint8_t *arena, espgpu_desc *desc, const uint32_t *frame, uint32_t n, espgpu_outsa *out,
                      uint32_t nout, const DevSA *sas, uint32_t nsas, uint8_t *fstatus, void *ws, void *stream);
+// espgpu_esp_classify_batch (classify.hip; the rule is classify.h's)
+int launch_esp_classify(const uint8_t *arena, const espgpu_pkt *pkt, uint32_t n, const espgpu_sad_entry *table,
+                        uint32_t nslots, uint32_t flags, espgpu_desc *desc, uint8_t *cstatus, void *stream);
 int launch_xfer(const XferSpan *spans, uint32_t nspans, const uint8_t *status, void *stream);
 int launch_replay_merge(uint8_t *status, const uint8_t *rstatus, uint32_t n, void *stream);
 int launch_plan(const espgpu_desc *d_desc, uint32_t n, const DevSA *sas, uint32_t nsas, uint32_t cap_sas,

@@ -101,6 +101,20 @@ OUT_ESN, OUT_CYCSEQ, OUT_WRAPCHECK, OUT_CTRCOMPAT = 0x01, 0x02, 0x04, 0x08
 OUT_PAD_SEQ, OUT_PAD_ZERO, OUT_PAD_RAND = 0x10, 0x20, 0x40
 
 
+class Pkt(C.Structure):
+    """struct espgpu_pkt: one received packet in the arena."""
+    _fields_ = [("off4", C.c_uint32), ("len", C.c_uint32)]
+
+
+class SadEntry(C.Structure):
+    """struct espgpu_sad_entry: one slot of the SPI table (key_allocsa's view of an SA)."""
+    _fields_ = [("spi", C.c_uint32), ("sa", C.c_uint16), ("proto", C.c_uint8), ("af", C.c_uint8),
+                ("salt", C.c_uint32), ("flags", C.c_uint32), ("dst", C.c_uint8 * 16)]
+
+
+CLS_IPCSUM, ENOENT, ENOTSUP = 0x1, 2, 95
+
+
 class Config(C.Structure):
     _fields_ = [("device", C.c_int), ("max_sessions", C.c_uint32),
                 ("batch_records", C.c_uint32), ("batch_bytes", C.c_uint32),
@@ -171,6 +185,9 @@ def lib():
         L.espgpu_esp_frame.argtypes = [C.POINTER(OutSA), C.POINTER(EShape), vp, C.c_uint32, C.c_uint32,
                                        C.c_uint8, C.POINTER(C.c_uint32)]
         L.espgpu_esp_frame_batch.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
+        L.espgpu_sad_build.argtypes = [vp, C.c_uint32, vp, C.c_uint32]
+        L.espgpu_esp_classify.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Desc)]
+        L.espgpu_esp_classify_batch.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.espgpu_last_kernel_ms.argtypes = [vp]
         L.espgpu_last_kernel_ms.restype = C.c_float
         L.espgpu_set_tuning.argtypes = [vp, C.c_char_p, C.c_int]

@@ -145,6 +145,43 @@ def esp_frame(driver, arena, desc, frame, n, outsa, fstatus, stream=None):
         raise RuntimeError("espgpu_esp_frame_batch: %s (%d)" % (driver.last_error(), rc))
 
 
+PKT_DTYPE = np.dtype([("off4", "<u4"), ("len", "<u4")])
+SAD_DTYPE = np.dtype([("spi", "<u4"), ("sa", "<u2"), ("proto", "u1"), ("af", "u1"), ("salt", "<u4"),
+                      ("flags", "<u4"), ("dst", "u1", (16,))])
+assert PKT_DTYPE.itemsize == 8 and SAD_DTYPE.itemsize == 32
+
+
+def sad_build(sas, nslots):
+    """The SPI table of espgpu_sad_build for a SAD_DTYPE array of SAs: a
+    SAD_DTYPE array of nslots slots, to be uploaded for esp_classify.
+    ValueError where the C function answers EINVAL."""
+    sas = np.ascontiguousarray(sas, dtype=SAD_DTYPE)
+    table = np.zeros(max(int(nslots), 1), dtype=SAD_DTYPE)
+    rc = L.lib().espgpu_sad_build(sas.ctypes.data, len(sas), table.ctypes.data, nslots)
+    if rc:
+        raise ValueError("espgpu_sad_build: %d" % rc)
+    return table[:nslots]
+
+
+def esp_classify(driver, arena, pkt, n, table, desc, cstatus, flags=0, stream=None):
+    """Inbound classification before replay_check (espgpu_esp_classify_batch):
+    pkt is a uint8 CUDA tensor of PKT_DTYPE records (where each received
+    packet's IP header starts and how many bytes it has), table the uploaded
+    result of sad_build.  desc receives one descriptor per packet, for the
+    rest of the inbound sequence, and cstatus 0 / EINVAL / ENOTSUP / ENOENT,
+    for replay_merge at its end; a refused packet's descriptor has len 0 and
+    sa 0xffff.  flags: L.CLS_IPCSUM."""
+    for t in (arena, pkt, table, desc, cstatus):
+        assert t.is_cuda and t.is_contiguous()
+    assert pkt.numel() >= n * PKT_DTYPE.itemsize and desc.numel() * desc.element_size() >= n * 16
+    nslots = table.numel() * table.element_size() // SAD_DTYPE.itemsize
+    rc = driver.lib.espgpu_esp_classify_batch(
+        driver.ctx, arena.data_ptr(), pkt.data_ptr(), n, table.data_ptr(), nslots, flags,
+        desc.data_ptr(), cstatus.data_ptr(), _stream_ptr(stream))
+    if rc:
+        raise RuntimeError("espgpu_esp_classify_batch: %s (%d)" % (driver.last_error(), rc))
+
+
 def replay_merge(driver, status, rstatus, n, stream=None):
     rc = driver.lib.espgpu_replay_merge(driver.ctx, status.data_ptr(), rstatus.data_ptr(), n,
                                         _stream_ptr(stream))

@@ -274,6 +274,96 @@ def esp_frame_host(outsa, shape, rec, rlen, next_header, esn_hi=0):
     return rc, hi.value
 
 
+IPPROTO_ESP, IPPROTO_AH = 50, 51
+IP_MF, IP_OFFMASK = 0x2000, 0x1fff
+
+
+def in_cksum(data):
+    """The Internet checksum of `data` (in_cksum): 0 for a header whose
+    checksum field is right."""
+    s = sum(struct.unpack(">%dH" % (len(data) // 2), bytes(data)))
+    while s >> 16:
+        s = (s & 0xffff) + (s >> 16)
+    return ~s & 0xffff
+
+
+def ipsec_input_classify(sadb, pkt, off4=0, ipcsum=False):
+    """What the stack does with a received packet up to esp_input's first
+    lines, for the packets the device path takes: ip_input's header checks
+    (ip_input.c:488-561, :807), ipsec_common_input's length check, SPI and
+    destination (ipsec_input.c:141-208), key_allocsa (key.c:1091-1133) and
+    esp_input's alignment check (xform_esp.c:279-284); ip6_input /
+    ipsec6_input for IPv6.  sadb maps an SPI to (sa, proto, af, dst bytes,
+    salt): one SPI namespace for all protocols.  Returns (status, (off4, len,
+    sa, esn_hi, salt)), the descriptor of the ESP record on status 0 and
+    (off4, 0, 0xffff, 0, 0) otherwise.  ENOTSUP marks the packets that go on
+    in the host stack: fragments (ip_reass), other protocols, IPv6 jumbograms
+    and link-local destinations."""
+    pkt = bytes(pkt)
+    n = len(pkt)
+
+    def drop(status):
+        return status, (off4, 0, 0xffff, 0, 0)
+
+    if n < 20:                                                       # m_pullup, ips_toosmall
+        return drop(L.EINVAL)
+    v = pkt[0] >> 4
+    if v == 4:
+        hlen = (pkt[0] & 0xf) << 2
+        if hlen < 20 or hlen > n:                                    # ips_badhlen
+            return drop(L.EINVAL)
+        if ipcsum and in_cksum(pkt[:hlen]) != 0:                     # ips_badsum
+            return drop(L.EINVAL)
+        ip_len, ip_off = struct.unpack(">H", pkt[2:4])[0], struct.unpack(">H", pkt[6:8])[0]
+        if ip_len < hlen or n < ip_len:                              # ips_badlen, ips_tooshort
+            return drop(L.EINVAL)
+        pkt = pkt[:ip_len]                                           # the trim, :555-561
+        if ip_off & (IP_MF | IP_OFFMASK):                            # ip_reass: the host's
+            return drop(L.ENOTSUP)
+        if pkt[9] != IPPROTO_ESP:
+            return drop(L.ENOTSUP)
+        af, skip, dst = 4, hlen, pkt[16:20]
+    elif v == 6:
+        if n < 40:
+            return drop(L.EINVAL)
+        plen = struct.unpack(">H", pkt[4:6])[0]
+        if plen == 0:                                                # jumbo payload option
+            return drop(L.ENOTSUP)
+        if n - 40 < plen:                                            # ip6s_tooshort
+            return drop(L.EINVAL)
+        pkt = pkt[:40 + plen]
+        if pkt[6] != IPPROTO_ESP:                                    # extension headers: the host's
+            return drop(L.ENOTSUP)
+        af, skip, dst = 6, 40, pkt[24:40]
+        if dst[0] == 0xfe and dst[1] & 0xc0 == 0x80:                 # IN6_IS_SCOPE_LINKLOCAL
+            return drop(L.ENOTSUP)
+    else:                                                            # ips_badvers
+        return drop(L.EINVAL)
+    if len(pkt) - skip < 8:                                          # ipsec_input.c:141
+        return drop(L.EINVAL)
+    if skip % 4 or len(pkt) % 4:                                     # xform_esp.c:279
+        return drop(L.EINVAL)
+    spi = struct.unpack(">I", pkt[skip:skip + 4])[0]
+    sav = sadb.get(spi) if spi else None                             # SAVHASH_HASH(spi)
+    if sav is None:
+        return drop(L.ENOENT)                                        # notdb
+    sa, proto, saf, sdst, salt = sav
+    if proto != IPPROTO_ESP or saf != af or bytes(sdst)[:len(dst)] != dst:   # key.c:1110-1118
+        return drop(L.ENOENT)
+    return 0, (off4 + skip // 4, len(pkt) - skip, sa, 0, salt)
+
+
+def esp_classify_host(table, pkt, off4=0, flags=0):
+    """espgpu_esp_classify, the engine's host rule, on a SAD_DTYPE table
+    (batch.sad_build) and a packet's bytes: (status, (off4, len, sa, esn_hi,
+    salt))."""
+    import ctypes as C
+    pkt = bytes(pkt)
+    d = L.Desc(0xdddddddd, 0xdddd, 0xdddd, 0xdddddddd, 0xdddddddd)
+    rc = L.lib().espgpu_esp_classify(table.ctypes.data, len(table), pkt, len(pkt), off4, flags, C.byref(d))
+    return rc, (d.off4, d.len, d.sa, d.esn_hi, d.salt)
+
+
 def trailer_word(plain_payload):
     """The 32-bit word the kernels' fused trailer check produces for a
     decrypted payload (espgpu_decrypt_batch_trailer, include/espgpu.h):

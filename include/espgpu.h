@@ -359,10 +359,14 @@ int  espgpu_decrypt_host(espgpu_ctx *ctx, const uint8_t *h_arena, uint64_t arena
  *
  * The inbound sequence on a device-resident batch, windows and bitmaps in
  * device memory from one batch to the next, all on one stream:
+ *   0. espgpu_esp_classify_batch   header sanity, SPI lookup; builds d_desc
+ *                                  from received packets (below; a caller that
+ *                                  has descriptors already starts at 1)
  *   1. espgpu_replay_check_batch   ipsec_chkreplay; fills desc.esn_hi
  *   2. espgpu_decrypt_batch        ICV check, decrypt (trailer checks)
  *   3. espgpu_replay_update_batch  ipsec_updatereplay for what authenticated
- *   4. espgpu_replay_merge, once with 1's and once with 3's result.
+ *   4. espgpu_replay_merge, once with 1's and once with 3's result, and a
+ *      third time with 0's: espgpu_replay_merge(d_status, d_cstatus, n).
  * espgpu_replay_update / _update64 are the same update on the host, one
  * record per call. */
 #define ESPGPU_REPLAY_ESN    0x1     /* SADB_X_SAFLAGS_ESN  */
@@ -524,6 +528,89 @@ int  espgpu_esp_frame(struct espgpu_outsa *o, const struct espgpu_eshape *shape,
 int  espgpu_esp_frame_batch(espgpu_ctx *ctx, uint8_t *d_arena, struct espgpu_desc *d_desc,
                             const uint32_t *d_frame, uint32_t n, struct espgpu_outsa *d_out,
                             uint32_t nout, uint8_t *d_fstatus, void *stream);
+
+/* ---- inbound classification (ip_input's header sanity, ipsec4_input /
+ *      ipsec6_input, ipsec_common_input's SPI lookup and esp_input's first
+ *      checks: freebsd/netinet/ip_input.c:488-561, :807,
+ *      netipsec/ipsec_input.c:116-226, key.c:1091-1133, xform_esp.c:279-284) ----
+ * Step 0 of the inbound sequence (replay block above): from received packets
+ * in the arena to the espgpu_desc every later step takes.
+ *
+ * The SPI table is open addressing with linear probing.  The home slot of an
+ * SPI is key_u32hash(spi) & (nslots - 1), the hash of the reference's SPI
+ * hash (key.c:258-259, :295-299: FNV-1 over the SPI's four network-order
+ * bytes); a slot with spi == 0 is free and ends a probe.  There is one SPI
+ * namespace for all protocols, and protocol, family and destination are
+ * compared only after the SPI matched, as key_allocsa does.  The table is
+ * read-only to every entry point: a changed SA set is a table rebuilt in
+ * another buffer, and stream order makes the switch safe. */
+struct espgpu_pkt {            /* 8 B: one received packet in the arena               */
+	uint32_t off4;             /* start of the IP header, in 4-byte units              */
+	uint32_t len;              /* bytes the buffer holds from there (m_pkthdr.len)     */
+};
+struct espgpu_sad_entry {      /* 32 B: one slot of the SPI table; spi == 0: free      */
+	uint32_t spi;              /* host order                                           */
+	uint16_t sa;               /* session id (espgpu_newsession's)                     */
+	uint8_t  proto;            /* 50 (ESP) or 51 (AH): saidx.proto                     */
+	uint8_t  af;               /* 4 or 6                                               */
+	uint32_t salt;             /* as espgpu_desc.salt; copied into the descriptor      */
+	uint32_t flags;            /* reserved, 0                                          */
+	uint8_t  dst[16];          /* saidx.dst: 4 bytes + 12 zeros for af 4               */
+};
+#define ESPGPU_CLS_IPCSUM 0x1  /* verify the IPv4 header checksum (ip_input.c:518-530) */
+/* Host: zero table[nslots] and insert sas[nsas] in order.  ESPGPU_EINVAL
+ * (table contents then unspecified) unless nslots is a power of two with
+ * nslots >= 2 * nsas (so a free slot ends every probe), and for an entry with
+ * spi 0, an SPI seen before (key.c:1106-1109), proto not 50 or 51, af not 4
+ * or 6, an af 4 entry whose dst[4..15] is not zero, or flags != 0. */
+int  espgpu_sad_build(const struct espgpu_sad_entry *sas, uint32_t nsas,
+                      struct espgpu_sad_entry *table, uint32_t nslots);
+/* Host: classify one packet of `len` bytes at `pkt`; `off4` is where it lies
+ * in the arena the descriptor will index.  Status 0 fills *desc = {off4 +
+ * skip / 4, record length, entry.sa, 0, entry.salt}; any other status fills
+ * {off4, 0, 0xffff, 0, 0}, which the replay check, the decrypt kernels and the
+ * window update all pass over.  Nothing is read outside [pkt, pkt + len), and
+ * of the packet nothing beyond the IP header and the SPI.  The checks, in
+ * order; the first that fires decides:
+ *   1. len < 20, version nibble neither 4 nor 6                      EINVAL
+ *   2. IPv4: hlen = ip_hl * 4 < 20, or hlen > len                    EINVAL
+ *      with ESPGPU_CLS_IPCSUM in flags, header checksum wrong        EINVAL
+ *      ip_len < hlen, or ip_len > len                                EINVAL
+ *        (bytes past ip_len are ignored: the trim, ip_input.c:555-561)
+ *      a fragment, ip_off & (IP_MF | IP_OFFMASK)                     ENOTSUP
+ *      ip_p != 50 (AH, IPComp, UDP-encapsulated ESP, non-IPsec)      ENOTSUP
+ *      ip_len - hlen < 8 (ipsec_input.c:141)                         EINVAL
+ *      ip_len & 3 (xform_esp.c:279)                                  EINVAL
+ *      skip = hlen, record length = ip_len - hlen
+ *   3. IPv6: len < 40                                                EINVAL
+ *      payload length 0 (jumbogram)                                  ENOTSUP
+ *      40 + plen > len                                               EINVAL
+ *      next header != 50 (extension headers are the host's)          ENOTSUP
+ *      destination in fe80::/10 (scope, ipsec_input.c:184-189)       ENOTSUP
+ *      plen < 8, or plen & 3                                         EINVAL
+ *      skip = 40, record length = plen
+ *   4. the SPI (big-endian dword at skip) is 0, no slot holds it, or the
+ *      slot's proto != 50, its af is not the packet's, or its dst is
+ *      not the packet's destination (4 or 16 bytes)                  ENOENT
+ * Fragments, AH and everything else answered ENOTSUP are the host stack's
+ * packets.  Not re-checked: the per-transform lengths (the decrypt kernels'
+ * EINVAL), whether session `sa` exists (theirs too), loopback and other
+ * address filters (ip_input's; the caller's).  A null or unusable table
+ * (nslots not a power of two) is EINVAL. */
+int  espgpu_esp_classify(const struct espgpu_sad_entry *table, uint32_t nslots,
+                         const uint8_t *pkt, uint32_t len, uint32_t off4, uint32_t flags,
+                         struct espgpu_desc *desc);
+/* The same rule for n packets of a device-resident arena: d_desc[i] and
+ * d_cstatus[i] are what espgpu_esp_classify gives for the packet at d_arena +
+ * d_pkt[i].off4 * 4.  d_table is the uploaded result of espgpu_sad_build, 16-
+ * byte aligned; d_arena is 4-byte aligned (EINVAL otherwise).  Writes d_desc
+ * and d_cstatus only.  Asynchronous, no workspace, no host round trip; n == 0
+ * is a no-op that returns 0. */
+int  espgpu_esp_classify_batch(espgpu_ctx *ctx, const uint8_t *d_arena,
+                               const struct espgpu_pkt *d_pkt, uint32_t n,
+                               const struct espgpu_sad_entry *d_table, uint32_t nslots,
+                               uint32_t flags, struct espgpu_desc *d_desc,
+                               uint8_t *d_cstatus, void *stream);
 
 /* Device time of the last timed batch's crypto kernels (ms, from HIP events
  * on the batch stream).  Process-path batches of <= 128 KiB (a burst on its
