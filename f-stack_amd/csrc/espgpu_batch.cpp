@@ -1,0 +1,497 @@
+// espgpu_batch.cpp — the kernel launches of the host runtime (espgpu_ctx.h):
+// run_batch, the device-resident batch entry points with the host-side
+// single-record rules beside them, and the host-to-host pipeline.
+#include "espgpu_ctx.h"
+
+#include "classify.h"      // (after the HIP runtime's vector types)
+
+namespace espgpu {
+namespace {
+
+int ensure_plan(espgpu_ctx *c, uint32_t n) {
+  const uint32_t need_chunks = plan_max_chunks(n, c->cfg.max_sessions);
+  if (n <= c->plan_cap && need_chunks <= c->max_chunks) return 0;
+  hipFree(c->d_work);
+  hipFree(c->d_order);
+  hipFree(c->d_chunks);
+  hipFree(c->d_nchunks);
+  c->plan_cap = std::max(n, 1024u);
+  c->max_chunks = plan_max_chunks(c->plan_cap, c->cfg.max_sessions);
+  // key histograms sized for the SA table's capacity: sessions created after
+  // this allocation must not outgrow it
+  HIPCHK(c, hipMalloc(&c->d_work, plan_workspace_words(c->cfg.max_sessions) * 4));
+  HIPCHK(c, hipMalloc(&c->d_order, (size_t)c->plan_cap * 4));
+  HIPCHK(c, hipMalloc(&c->d_chunks, (size_t)c->max_chunks * sizeof(Chunk)));
+  HIPCHK(c, hipMalloc(&c->d_nchunks, 16));
+  c->plan_dirty = true;
+  return 0;
+}
+
+// Around the launches that use what is per ctx (work-queue counters, planner
+// and replay workspaces): stream-ordered after the ctx's last launch, which
+// this one then becomes.
+int launch_begin(espgpu_ctx *c, hipStream_t st) {
+  if (c->launched && st != c->last_st) HIPCHK(c, hipStreamWaitEvent(st, c->ev_last, 0));
+  return 0;
+}
+int launch_end(espgpu_ctx *c, hipStream_t st) {
+  HIPCHK(c, hipEventRecord(c->ev_last, st));
+  c->last_st = st;
+  c->launched = true;
+  return 0;
+}
+
+}  // namespace
+
+// Launch the crypto kernels for one batch of device-resident records.
+// kinds: which kernels the batch needs (1 GCM, 2 ETA); the device-resident
+// entry points do not know and pass both, with 8: DIGEST (AH) records under
+// the batch path's semantics.  4: a process-path batch with DIGEST requests
+// (swcr_authcompute's semantics: DigestParams::op 2).
+int run_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n, uint8_t *d_status,
+              uint8_t *d_out, uint32_t flags, int encrypt, hipStream_t st, uint32_t *d_trailer, uint32_t kinds,
+              const StageLists *stage, uint32_t out_stride) {
+  if (c->failed) return ESPGPU_EIO;
+  if (n == 0) return 0;
+  if (out_stride && (c->n_eta > 0 || c->n_dig > 0))
+    return fail(c, ESPGPU_ENOTSUP, "packed output serves contexts with GCM sessions only");
+  if (take_launch_fault(c)) return ESPGPU_EIO;
+  door_retire(c);
+  int e = launch_begin(c, st);
+  if (e) return e;
+  const uint32_t nsas = (uint32_t)c->sessions.size();
+  GcmParams p{};
+  p.arena = d_arena;
+  p.out = encrypt ? d_arena : (d_out ? d_out : d_arena);
+  p.desc = d_desc;
+  p.n = n;
+  p.sas = c->d_sas;
+  p.gtab = c->d_gtab;
+  p.tpair = c->d_tpair;
+  p.status = d_status;
+  p.nsas = nsas;
+  p.queue = c->d_queue;
+  p.trailer = encrypt ? nullptr : d_trailer;
+  p.out_stride = out_stride;
+  if (stage) {
+    p.xin = stage->xin;
+    p.xout = stage->xout;
+    p.hstat = stage->hstat;
+    p.hdesc = stage->hdesc;
+  }
+  if (!(flags & ESPGPU_BATCH_GROUPED)) {
+    if ((e = ensure_plan(c, n))) return e;
+    // the key counts start at zero: plan_scatter zeroes them after use, so
+    // only a fresh workspace (or one a failed launch left behind) needs it
+    if (c->plan_dirty) {
+      HIPCHK(c, hipMemsetAsync(c->d_work, 0, plan_workspace_words(c->cfg.max_sessions) * 4, st));
+      c->plan_dirty = false;
+    }
+    if (launch_plan(d_desc, n, c->d_sas, nsas, c->cfg.max_sessions, c->d_work, c->d_order, c->d_chunks, c->d_nchunks,
+                    c->max_chunks, st)) {
+      c->plan_dirty = true;
+      return fail(c, ESPGPU_EIO, "planner launch failed (%u sessions)", nsas);
+    }
+    p.order = c->d_order;
+    p.chunks = c->d_chunks;
+    p.nchunks = c->d_nchunks;
+  }
+  const int two_pass = (!encrypt && p.out == d_arena);
+  // E_K(J0) scratch: the burst kernel (small batches of <= gcm_burst records,
+  // out of place or encrypt; launch_gcm picks the kernel from it)
+  const bool gsmall = c->gcm_lanes ? c->gcm_lanes == kGcmLanesSmall : n < kGcmSmallBatch;
+  // (packed output: the fused kernel only)
+  if ((kinds & 1) && !out_stride &&
+      gsmall && !two_pass && n <= c->gcm_burst) {
+    if (n > c->ej0_cap) {
+      hipFree(c->d_ej0);
+      c->d_ej0 = nullptr;
+      c->ej0_cap = 0;
+      HIPCHK(c, hipMalloc(&c->d_ej0, (size_t)n * sizeof(uint4)));
+      c->ej0_cap = n;
+    }
+    p.ej0 = c->d_ej0;
+  }
+  // beside a running doorbell kernel (one workgroup per CU on door_wg CUs)
+  // the other kernels take the remaining CUs: every workgroup of theirs must
+  // run for the launch to finish
+  int grid = c->cfg.grid ? (int)c->cfg.grid : 256;
+  if (c->door_live && !door_exited(c)) grid = std::max(1, grid - c->door_wg);
+  // A context without GCM sessions still launches the GCM kernel for the
+  // records whose session is invalid (EINVAL; the planner chunks them with the
+  // GCM records), but a few workgroups do: the others would only draw a
+  // ticket past the end (cfg3: ~9 us -> ~3 us per batch)
+  const int ggrid = c->n_gcm > 0 ? grid : std::min(grid, 16);
+  if ((kinds & 1) && launch_gcm(p, encrypt, two_pass, ggrid, c->gcm_lanes, st))
+    return fail(c, ESPGPU_EIO, "GCM kernel launch failed");
+  if ((kinds & 2) && c->n_eta > 0) {
+    EtaParams q{};
+    q.arena = d_arena;
+    q.out = p.out;
+    q.desc = d_desc;
+    q.order = p.order;
+    q.chunks = p.chunks;
+    q.nchunks = p.nchunks;
+    q.queue = c->d_queue + kQueueRegionWords;
+    q.trailer = p.trailer;
+    q.n = n;
+    q.sas = c->d_sas;
+    q.tpair = c->d_tpair;
+    q.dpair = c->d_dpair;
+    q.isbox = c->d_isbox;
+    q.status = d_status;
+    q.nsas = nsas;
+    const int ek = (c->n_cbc > 0 ? 1 : 0) | (c->n_ctr > 0 ? 2 : 0) | (c->n_wcbc > 0 ? 4 : 0) |
+                   (c->n_wctr > 0 ? 8 : 0) | (c->n_whash > 0 ? 16 : 0);
+    if (launch_eta(q, encrypt, ek, grid, st))
+      return fail(c, ESPGPU_EIO, "ETA kernel launch failed");
+  }
+  // AH digest sessions: launched only while the context has some
+  if (c->n_dig > 0 && (kinds & 12)) {
+    DigestParams g{};
+    g.arena = d_arena;
+    g.icv_out = p.out;
+    g.desc = d_desc;
+    g.order = p.order;
+    g.chunks = p.chunks;
+    g.nchunks = p.nchunks;
+    g.queue = c->d_queue + 3 * kQueueRegionWords;
+    g.trailer = p.trailer;
+    g.n = n;
+    g.sas = c->d_sas;
+    g.status = d_status;
+    g.nsas = nsas;
+    g.op = (kinds & 4) ? 2u : (encrypt ? 1u : 0u);
+    if (launch_digest(g, c->n_dig > c->n_dig_wide, c->n_dig_wide > 0, grid, st))
+      return fail(c, ESPGPU_EIO, "digest kernel launch failed");
+  }
+  return launch_end(c, st);
+}
+
+namespace {
+
+// The device-resident entry points: a launch that could not be queued (EIO)
+// fails the ctx as a process-path launch does (later calls answer EIO).
+int batch_rc(espgpu_ctx *c, int e) {
+  if (e == ESPGPU_EIO && !c->failed) ctx_fail(c, "batch launch failed");
+  return e;
+}
+
+// The workspace grows with n and nreplay and is kept.  An allocation that
+// fails is ENOMEM with nothing launched and the ctx healthy.
+int ensure_replay_ws(espgpu_ctx *c, uint32_t n, uint32_t nreplay) {
+  if (c->d_replay_ws && n <= c->replay_ws_n && nreplay <= c->replay_ws_sas) return 0;
+  const uint32_t cap_n = std::max({n, c->replay_ws_n, 1024u}), cap_sas = std::max(nreplay, c->replay_ws_sas);
+  hipFree(c->d_replay_ws);               // (waits for the launches that use it)
+  c->d_replay_ws = nullptr;
+  c->replay_ws_n = c->replay_ws_sas = 0;
+  const size_t bytes = replay_update_workspace_bytes(cap_n, cap_sas);
+  if (hipMalloc(&c->d_replay_ws, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    c->d_replay_ws = nullptr;
+    return fail(c, ESPGPU_ENOMEM, "replay update workspace: %zu bytes of device memory not available", bytes);
+  }
+  c->replay_ws_n = cap_n;
+  c->replay_ws_sas = cap_sas;
+  return 0;
+}
+
+int host_pipeline(espgpu_ctx *c, const uint8_t *h_arena, uint64_t arena_bytes,
+                  const espgpu_desc *h_desc, uint32_t n, uint8_t *h_status, uint8_t *h_out,
+                  uint32_t chunk, uint32_t flags, int encrypt) {
+  if (!c || !h_arena || !h_desc || !h_status || (!encrypt && !h_out)) return ESPGPU_EINVAL;
+  if (n == 0) return 0;
+  if (!chunk) chunk = 65536;
+  if (arena_bytes + 64 > c->e2e_bytes || n > c->e2e_n) {
+    hipFree(c->e2e_arena); hipFree(c->e2e_out); hipFree(c->e2e_status); hipFree(c->e2e_desc);
+    c->e2e_bytes = arena_bytes + 64;
+    c->e2e_n = n;
+    HIPCHK(c, hipMalloc(&c->e2e_arena, c->e2e_bytes));
+    HIPCHK(c, hipMalloc(&c->e2e_out, c->e2e_bytes));
+    HIPCHK(c, hipMalloc(&c->e2e_status, n));
+    HIPCHK(c, hipMalloc(&c->e2e_desc, (size_t)n * sizeof(espgpu_desc)));
+  }
+  // Chunks of consecutive records (descriptors in ascending arena order) map to
+  // contiguous byte ranges, copied to the same offsets of a device mirror so the
+  // descriptors are used unchanged.
+  for (uint32_t i0 = 0, k = 0; i0 < n; i0 += chunk, ++k) {
+    const uint32_t i1 = std::min(n, i0 + chunk), m = i1 - i0;
+    uint64_t lo = (uint64_t)h_desc[i0].off4 * 4, hi = 0;
+    for (uint32_t i = i0; i < i1; ++i) {
+      const uint64_t o = (uint64_t)h_desc[i].off4 * 4;
+      lo = std::min(lo, o);
+      hi = std::max(hi, o + h_desc[i].len);
+    }
+    hi = std::min(arena_bytes, hi + 16);                 // partial-block loads read <= 16 B past
+    hipEvent_t ein = c->e2e_in[k & 1], ek = c->e2e_k[k & 1];
+    HIPCHK(c, hipMemcpyAsync(c->e2e_desc + i0, h_desc + i0, m * sizeof(espgpu_desc), hipMemcpyHostToDevice, c->s_in));
+    HIPCHK(c, hipMemcpyAsync(c->e2e_arena + lo, h_arena + lo, hi - lo, hipMemcpyHostToDevice, c->s_in));
+    HIPCHK(c, hipEventRecord(ein, c->s_in));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, ein, 0));
+    int e = run_batch(c, c->e2e_arena, c->e2e_desc + i0, m, c->e2e_status + i0,
+                      encrypt ? nullptr : c->e2e_out, flags, encrypt, c->stream);
+    if (e) return e;
+    HIPCHK(c, hipEventRecord(ek, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->s_out, ek, 0));
+    uint8_t *dst = encrypt ? (uint8_t *)h_arena : h_out;
+    HIPCHK(c, hipMemcpyAsync(dst + lo, (encrypt ? c->e2e_arena : c->e2e_out) + lo, hi - lo, hipMemcpyDeviceToHost, c->s_out));
+    HIPCHK(c, hipMemcpyAsync(h_status + i0, c->e2e_status + i0, m, hipMemcpyDeviceToHost, c->s_out));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->s_out));
+  return 0;
+}
+
+}  // namespace
+}  // namespace espgpu
+
+using namespace espgpu;
+
+extern "C" {
+
+int espgpu_replay_params_ok(const espgpu_replay *r) {
+  if (!r) return 0;
+  if (r->wsize == 0) return 1;
+  const uint32_t b = r->bitmap_size;
+  return b != 0 && (b & (b - 1)) == 0 && (uint64_t)b * 32 >= (uint64_t)r->wsize * 8;
+}
+
+int espgpu_replay_check_batch(espgpu_ctx *c, const uint8_t *d_arena, espgpu_desc *d_desc, uint32_t n,
+                              const espgpu_replay *d_replay, uint32_t nreplay, const uint32_t *d_bitmap,
+                              uint8_t *d_rstatus, void *stream) {
+  if (!c || (n && (!d_arena || !d_desc || !d_rstatus || (nreplay && (!d_replay || !d_bitmap)))))
+    return ESPGPU_EINVAL;
+  if (launch_replay_check(d_arena, d_desc, n, d_replay, nreplay, d_bitmap, d_rstatus, stream))
+    return fail(c, ESPGPU_EIO, "replay check kernel launch failed");
+  return 0;
+}
+
+int espgpu_replay_merge(espgpu_ctx *c, uint8_t *d_status, const uint8_t *d_rstatus, uint32_t n, void *stream) {
+  if (!c || (n && (!d_status || !d_rstatus))) return ESPGPU_EINVAL;
+  if (launch_replay_merge(d_status, d_rstatus, n, stream))
+    return fail(c, ESPGPU_EIO, "replay merge kernel launch failed");
+  return 0;
+}
+
+// ipsec_updatereplay (freebsd/netipsec/ipsec.c:1338-1436) with the window
+// helpers advance_window / set_window (:1203-1232): after authentication, in
+// arrival order per SA.
+int espgpu_replay_update(espgpu_replay *r, uint32_t *bitmap, uint32_t seq) {
+  if (!r || (r->wsize && !bitmap)) return ESPGPU_EINVAL;
+  if (r->wsize == 0) return 0;
+  // the window indexes the bitmap with bitmap_size - 1 as a mask: a power of
+  // two covering wsize * 8 bits (key.c:3346-3351 sizes it so)
+  if (!espgpu_replay_params_ok(r)) return ESPGPU_EINVAL;
+  if (seq == 0 && r->last == 0) return ESPGPU_EACCES;
+  uint32_t *bm = bitmap + r->bitmap_off;
+  const uint32_t mask = r->bitmap_size - 1;
+  auto seen = [&](uint32_t s) { return (bm[(s >> 5) & mask] >> (s & 31)) & 1u; };
+  auto mark = [&](uint32_t s) { bm[(s >> 5) & mask] |= 1u << (s & 31); };
+  auto advance = [&](uint64_t s) {      // clear the words the window top moves past
+    const uint64_t cur = r->last >> 5;
+    uint64_t diff = (s >> 5) - cur;
+    if (diff > r->bitmap_size) diff = r->bitmap_size;
+    for (uint64_t k = 0; k < diff; ++k) bm[(k + cur + 1) & mask] = 0;
+  };
+  const uint32_t window = r->wsize << 3;
+  const uint32_t tl = (uint32_t)r->last, th = (uint32_t)(r->last >> 32);
+  const uint32_t bl = tl - window + 1;
+  if ((tl >= window - 1 && seq >= bl) || (tl < window - 1 && seq < bl)) {
+    if (seq <= tl) {
+      if (seen(seq)) return ESPGPU_EACCES;
+      mark(seq);
+    } else {
+      const uint64_t s = ((uint64_t)th << 32) | seq;
+      advance(s);
+      mark(seq);
+      r->last = s;
+    }
+    return 0;
+  }
+  if (!(r->flags & ESPGPU_REPLAY_ESN)) return ESPGPU_EACCES;
+  if (tl < window - 1 && seq >= bl) {   // in the window, previous subspace
+    if (th == 0 || seen(seq)) return ESPGPU_EACCES;
+    mark(seq);
+    return 0;
+  }
+  if (th + 1 == 0) return ESPGPU_EACCES;   // the high part would wrap
+  const uint64_t s = ((uint64_t)(th + 1) << 32) | seq;
+  advance(s);
+  mark(seq);
+  r->last = s;
+  return 0;
+}
+
+// The same update on the 64-bit sequence number the record was authenticated
+// under (ESN: esn_hi << 32 | seq; else seq): nothing is inferred, so a record
+// that has fallen below the window is refused, never taken for the next
+// subspace.  The rule espgpu_replay_update_batch applies (replay.hip).
+int espgpu_replay_update64(espgpu_replay *r, uint32_t *bitmap, uint64_t seq64) {
+  if (!r || (r->wsize && !bitmap)) return ESPGPU_EINVAL;
+  if (r->wsize == 0) return 0;
+  const uint64_t window = (uint64_t)r->wsize << 3;
+  // as espgpu_replay_update, and the redundant block (key.c:3343-3351): a
+  // ring of at least window + 32 bits, or two sequence numbers of one window
+  // span could share a bit
+  if (!espgpu_replay_params_ok(r) || (uint64_t)r->bitmap_size * 32 < window + 32) return ESPGPU_EINVAL;
+  const uint64_t s = (r->flags & ESPGPU_REPLAY_ESN) ? seq64 : (uint32_t)seq64, top = r->last;
+  if (s == 0 && top == 0) return ESPGPU_EACCES;
+  uint32_t *bm = bitmap + r->bitmap_off;
+  const uint64_t mask = r->bitmap_size - 1;
+  uint32_t &word = bm[(s >> 5) & mask];
+  const uint32_t bit = 1u << (s & 31);
+  if (s > top) {
+    uint64_t diff = (s >> 5) - (top >> 5);          // clear the words the top moves past
+    if (diff > r->bitmap_size) diff = r->bitmap_size;
+    for (uint64_t k = 0; k < diff; ++k) bm[(k + (top >> 5) + 1) & mask] = 0;
+    word |= bit;
+    r->last = s;
+    return 0;
+  }
+  if (top - s >= window) return ESPGPU_EACCES;      // below the window
+  if (word & bit) return ESPGPU_EACCES;
+  word |= bit;
+  return 0;
+}
+
+int espgpu_replay_update_batch(espgpu_ctx *c, const uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n,
+                               const uint8_t *d_status, espgpu_replay *d_replay, uint32_t nreplay,
+                               uint32_t *d_bitmap, uint8_t *d_ustatus, void *stream) {
+  if (!c || (n && (!d_arena || !d_desc || !d_status || !d_ustatus || (nreplay && (!d_replay || !d_bitmap)))))
+    return ESPGPU_EINVAL;
+  if (c->failed) return ESPGPU_EIO;
+  if (n == 0) return 0;
+  int e = ensure_replay_ws(c, n, nreplay);
+  if (e) return e;
+  if (take_launch_fault(c)) return batch_rc(c, ESPGPU_EIO);
+  // the workspace is per ctx, as the planner's: stream-ordered after the last launch
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if ((e = launch_begin(c, st))) return batch_rc(c, e);
+  if (launch_replay_update(d_arena, d_desc, n, d_status, d_replay, nreplay, d_bitmap, d_ustatus, c->d_replay_ws, st))
+    return batch_rc(c, fail(c, ESPGPU_EIO, "replay update launch failed"));
+  return batch_rc(c, launch_end(c, st));
+}
+
+// ---- outbound framing ----------------------------------------------------------
+// The shape from session parameters, through the fields newsession keeps in
+// DevSA (mode, calg, mlen: session_filed), so the host rule and the kernels
+// read one table.
+int espgpu_esp_frame_shape(const espgpu_session_params *csp, uint32_t flags, espgpu_eshape *shape) {
+  if (!csp || !shape || probe_caps(csp) >= 0) return ESPGPU_EINVAL;
+  uint32_t mode, mlen;
+  session_filed(csp, &mode, &mlen);
+  espgpu_eshape s;
+  if (!esp_shape_of(mode, (uint32_t)csp->csp_cipher_alg, mlen, flags, &s)) return ESPGPU_EINVAL;
+  *shape = s;
+  return 0;
+}
+
+// esp_output between m_makespace and crypto_dispatch (xform_esp.c:703-716,
+// :782-887) for one record.  The rule espgpu_esp_frame_batch applies (replay.hip).
+int espgpu_esp_frame(espgpu_outsa *o, const espgpu_eshape *s, uint8_t *rec, uint32_t len, uint32_t rlen,
+                     uint8_t next_header, uint32_t *esn_hi) {
+  if (!o || !s || !rec || !esn_hi) return ESPGPU_EINVAL;
+  if ((s->ivlen != 0 && s->ivlen != 8 && s->ivlen != 16) || (s->blks != 4 && s->blks != 16)) return ESPGPU_EINVAL;
+  if (rlen > 0xffffu || 8 + s->ivlen + rlen + esp_padding(rlen, s->blks) + s->alen != len) return ESPGPU_EINVAL;
+  if (esp_out_room(o->count, o->flags) == 0) return ESPGPU_EINVAL;
+  o->count++;                                                    // :793
+  const uint64_t cntr = o->cntr;
+  if (s->ivlen == 8) o->cntr++;                                  // :802-803
+  esp_frame_write(rec, *s, o->flags, o->spi, o->count, cntr, rlen, next_header);
+  *esn_hi = (o->flags & ESPGPU_OUT_ESN) ? (uint32_t)(o->count >> 32) : 0u;   // :799
+  return 0;
+}
+
+int espgpu_esp_frame_batch(espgpu_ctx *c, uint8_t *d_arena, espgpu_desc *d_desc, const uint32_t *d_frame,
+                           uint32_t n, espgpu_outsa *d_out, uint32_t nout, uint8_t *d_fstatus, void *stream) {
+  if (!c || (n && (!d_arena || !d_desc || !d_frame || !d_fstatus || (nout && !d_out)))) return ESPGPU_EINVAL;
+  if (c->failed) return ESPGPU_EIO;
+  if (n == 0) return 0;
+  // the replay update's workspace holds this one's too (esp_frame_workspace_bytes)
+  int e = ensure_replay_ws(c, n, nout);
+  if (e) return e;
+  if (take_launch_fault(c)) return batch_rc(c, ESPGPU_EIO);
+  // the workspace is per ctx: stream-ordered after the last launch
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if ((e = launch_begin(c, st))) return batch_rc(c, e);
+  if (launch_esp_frame(d_arena, d_desc, d_frame, n, d_out, nout, c->d_sas, c->cfg.max_sessions, d_fstatus,
+                       c->d_replay_ws, st))
+    return batch_rc(c, fail(c, ESPGPU_EIO, "esp frame launch failed"));
+  return batch_rc(c, launch_end(c, st));
+}
+
+// ---- inbound classification ----------------------------------------------------
+int espgpu_sad_build(const espgpu_sad_entry *sas, uint32_t nsas, espgpu_sad_entry *table, uint32_t nslots) {
+  return sad_build(sas, nsas, table, nslots);
+}
+
+// ip_input's header sanity, ipsec_common_input's lookup and esp_input's first
+// checks for one packet.  The rule espgpu_esp_classify_batch applies (classify.h).
+int espgpu_esp_classify(const espgpu_sad_entry *table, uint32_t nslots, const uint8_t *pkt, uint32_t len,
+                        uint32_t off4, uint32_t flags, espgpu_desc *desc) {
+  if (!desc) return ESPGPU_EINVAL;
+  if (!table || nslots == 0 || (nslots & (nslots - 1)) || (!pkt && len) || (flags & ~(uint32_t)ESPGPU_CLS_IPCSUM)) {
+    *desc = espgpu_desc{off4, 0, 0xffff, 0, 0};
+    return ESPGPU_EINVAL;
+  }
+  return esp_classify_rule(table, nslots, pkt, len, off4, flags, desc);
+}
+
+int espgpu_esp_classify_batch(espgpu_ctx *c, const uint8_t *d_arena, const espgpu_pkt *d_pkt, uint32_t n,
+                              const espgpu_sad_entry *d_table, uint32_t nslots, uint32_t flags, espgpu_desc *d_desc,
+                              uint8_t *d_cstatus, void *stream) {
+  if (!c || (flags & ~(uint32_t)ESPGPU_CLS_IPCSUM)) return ESPGPU_EINVAL;
+  if (n && (!d_arena || !d_pkt || !d_table || !d_desc || !d_cstatus || nslots == 0 || (nslots & (nslots - 1)) ||
+            ((uintptr_t)d_arena & 3) || ((uintptr_t)d_table & 15)))
+    return ESPGPU_EINVAL;
+  if (c->failed) return ESPGPU_EIO;
+  if (n == 0) return 0;
+  if (take_launch_fault(c)) return batch_rc(c, ESPGPU_EIO);
+  // no workspace and nothing of the ctx's is touched: the caller's stream orders it
+  if (launch_esp_classify(d_arena, d_pkt, n, d_table, nslots, flags, d_desc, d_cstatus, stream))
+    return batch_rc(c, fail(c, ESPGPU_EIO, "classify kernel launch failed"));
+  return 0;
+}
+
+int espgpu_decrypt_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n,
+                         uint8_t *d_status, uint8_t *d_out, uint32_t flags, void *stream) {
+  if (!c || (!d_arena && n) || (!d_desc && n) || (!d_status && n)) return ESPGPU_EINVAL;
+  return batch_rc(c, run_batch(c, d_arena, d_desc, n, d_status, d_out ? d_out : d_arena, flags, 0,
+                             reinterpret_cast<hipStream_t>(stream)));
+}
+
+int espgpu_decrypt_batch_trailer(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc,
+                                 uint32_t n, uint8_t *d_status, uint8_t *d_out, uint32_t *d_trailer,
+                                 uint32_t flags, void *stream) {
+  if (!c || (!d_arena && n) || (!d_desc && n) || (!d_status && n) || (!d_trailer && n)) return ESPGPU_EINVAL;
+  return batch_rc(c, run_batch(c, d_arena, d_desc, n, d_status, d_out ? d_out : d_arena, flags, 0,
+                             reinterpret_cast<hipStream_t>(stream), d_trailer));
+}
+
+int espgpu_decrypt_batch_packed(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n,
+                                uint8_t *d_status, uint8_t *d_out, uint32_t out_stride, uint32_t flags,
+                                void *stream) {
+  if (!c || (!d_arena && n) || (!d_desc && n) || (!d_status && n) || (!d_out && n) || d_out == d_arena ||
+      out_stride == 0 || out_stride % 128 != 0 || ((uintptr_t)d_out & 127))
+    return ESPGPU_EINVAL;
+  return batch_rc(c, run_batch(c, d_arena, d_desc, n, d_status, d_out, flags, 0, reinterpret_cast<hipStream_t>(stream),
+                             nullptr, 3, nullptr, out_stride));
+}
+
+int espgpu_encrypt_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n,
+                         uint8_t *d_status, uint32_t flags, void *stream) {
+  if (!c || (!d_arena && n) || (!d_desc && n) || (!d_status && n)) return ESPGPU_EINVAL;
+  return batch_rc(c, run_batch(c, d_arena, d_desc, n, d_status, nullptr, flags, 1, reinterpret_cast<hipStream_t>(stream)));
+}
+
+float espgpu_last_kernel_ms(espgpu_ctx *c) { return c ? c->last_ms : 0.f; }
+
+int espgpu_decrypt_host(espgpu_ctx *c, const uint8_t *h_arena, uint64_t arena_bytes,
+                        const espgpu_desc *h_desc, uint32_t n, uint8_t *h_status, uint8_t *h_out,
+                        uint32_t chunk, uint32_t flags) {
+  if (c && c->failed) return ESPGPU_EIO;
+  if (c && c->n_dig > 0)
+    return fail(c, ESPGPU_ENOTSUP, "the host pipeline does not serve contexts with DIGEST sessions");
+  return batch_rc(c, host_pipeline(c, h_arena, arena_bytes, h_desc, n, h_status, h_out, chunk, flags, 0));
+}
+
+}  // extern "C"

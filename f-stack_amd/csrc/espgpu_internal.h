@@ -1,10 +1,11 @@
 // espgpu_internal.h — device-side data layouts shared by the host runtime
-// (espgpu.cpp) and the HIP kernels (esp_gcm.hip, esp_cbc.hip, esp_ah.hip,
+// (espgpu*.cpp) and the HIP kernels (esp_gcm.hip, esp_cbc.hip, esp_ah.hip,
 // plan.hip, replay.hip, classify.hip, xfer.hip).
 #pragma once
 #include <stdint.h>
 
 #include "espgpu.h"
+#include "req_shape.h"
 
 namespace espgpu {
 
@@ -122,7 +123,7 @@ struct EtaParams {
 
 // AH digest sessions (esp_ah.hip digest_kernel): lane = record HMAC over the
 // whole record, any byte length.
-constexpr uint32_t kDigVerifyBit = 0x80000000u;   // driver path: desc.salt bit 31 = VERIFY_DIGEST
+// (kDigVerifyBit, req_shape.h: the driver path's desc.salt bit 31 = VERIFY_DIGEST)
 struct DigestParams {
   const uint8_t *arena;           // records (read only)
   uint8_t *icv_out;               // computed ICVs go to icv_out + record offset + ICV offset
@@ -221,7 +222,7 @@ struct DoorArgs {
   uint32_t nsas;
 };
 
-// Launchers (defined in the .hip files, called by espgpu.cpp).
+// Launchers (defined in the .hip files, called by espgpu*.cpp).
 int launch_gcm_door(const DoorArgs &a, int grid, void *stream);
 // lanes: 0 = by batch size (kGcmLanesSmall below kGcmSmallBatch records,
 // else kGcmLanesPerRec), or force 4 / 8 (set_tuning "gcm_lanes", tests)

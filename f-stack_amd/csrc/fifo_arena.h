@@ -1,4 +1,4 @@
-// fifo_arena.h — the host overflow's fixed-capacity FIFO allocator (espgpu.cpp
+// fifo_arena.h — the host overflow's fixed-capacity FIFO allocator (espgpu_ctx.h
 // Overflow), in a header of its own so the CPU self-test
 // (tools/fifo_selftest.cpp) checks the same code against a reference deque.
 #pragma once

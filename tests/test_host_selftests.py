@@ -44,6 +44,25 @@ def test_bitsliced_aes_selftest(tmp_path):
     assert r.stdout.startswith("OK")
 
 
+def test_request_rule_selftest(tmp_path):
+    """The ESP / AH request rule in front of espgpu_process's staging
+    (req_shape.h: req_plan, req_gather), on the CPU without HIP: for GCM
+    (with and without SEPARATE_AAD, ICV 8 / 12 / 16), CBC / CTR / ESP-NULL
+    with HMAC and cipher-only, and AH compute / verify with and without ESN,
+    accepted requests at the smallest payload and as a 1480-byte record over
+    one to four segments -- record length, header, salt, ESN, kind, result
+    spans and the gathered record against numbers written out in the test --
+    and one rejected request per condition of the rule
+    (tools/req_shape_selftest.cpp)."""
+    exe = tmp_path / "req_shape_selftest"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"),
+                    "-I", os.path.join(ROOT, "f-stack_amd", "csrc"), "-o", str(exe),
+                    os.path.join(ROOT, "tools", "req_shape_selftest.cpp")], check=True, timeout=300)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:]
+    assert r.stdout.startswith("OK")
+
+
 def test_overflow_fifo_arena_selftest(tmp_path):
     """The host overflow's allocator (fifo_arena.h: a bip buffer of
     variable-length allocations, freed oldest first): 200 random alloc / pop

@@ -49,7 +49,7 @@ int main() {
       for (int i = 0; i < klen; ++i) key[i] = (uint8_t)rnd();
       uint32_t rk[60];
       const int nr = hc::aes_expand_enc(key, klen, rk);
-      // the DevSA::dk form (espgpu.cpp newsession): little-endian words, K_r ^ 0x63.. for r >= 1
+      // the round keys as aes_bs.h takes them (no session keeps this form: built here): little-endian words, K_r ^ 0x63.. for r >= 1
       uint32_t dk[60];
       for (int i = 0; i < 4 * (nr + 1); ++i) dk[i] = bswap(rk[i]) ^ (i >= 4 ? 0x63636363u : 0u);
       // a window: counters 32w .. 32w+31 of one record's nonce (salt || IV)

@@ -1,5 +1,5 @@
 // CPU self-test of the host overflow's allocator (f-stack_amd/csrc/fifo_arena.h,
-// espgpu.cpp Overflow): random alloc / pop sequences, with wraps, undos of
+// espgpu_ctx.h Overflow): random alloc / pop sequences, with wraps, undos of
 // partial allocations and an empty arena that restarts at 0, checked against a
 // reference model -- every live allocation lies inside the arena, no two
 // overlap, pops come back oldest first, and an allocation is refused only when
