@@ -359,24 +359,42 @@ __device__ __forceinline__ void aes_ctr2(const CtrCache &cc, uint32_t ca, uint32
   uint32_t a2 = cc.L2 ^ ror16(te0(lds, tpa(ta, slot, 1))), b2 = cc.L2 ^ ror16(te0(lds, tpa(tb, slot, 1)));
   uint32_t a3 = cc.L3 ^ te1(lds, tpa(ta, slot, 2)), b3 = cc.L3 ^ te1(lds, tpa(tb, slot, 2));
   __builtin_amdgcn_sched_barrier(0);
+  if (!W) {
+    // Two rounds per key fetch.  A scalar load returns out of order against
+    // the LDS reads, so while one is pending the next wait for a table read
+    // has to drain the whole counter: one fetch (s_load_dwordx8) per two
+    // rounds halves those drains.  Rounds 3..nr are an even number of rounds
+    // for every key length, so the last pair is (round nr - 1, last round).
+    // (Rounds 3-10's keys held in 32 SGPRs for the record group, the rounds
+    // unrolled, did not stay in SGPRs: they went to scratch and came back as
+    // one vector load per round)
 #pragma unroll 1
-  for (int r = 3; r < ((gopts() & 4) ? 3 : nr); ++r) {
-    const uint4 k = ldk4(rk + 4 * r);
-    if (W) {
-      aes_round2w(a0, a1, a2, a3, b0, b1, b2, b3, k, lds, slot);
-    } else {
-      aes_round(a0, a1, a2, a3, k, lds, slot);
-      aes_round(b0, b1, b2, b3, k, lds, slot);
+    for (int r = 3; r < ((gopts() & 4) ? 3 : nr - 1); r += 2) {
+      const uint4 k0 = ldk4(rk + 4 * r), k1 = ldk4(rk + 4 * r + 4);
+      aes_round(a0, a1, a2, a3, k0, lds, slot);
+      aes_round(b0, b1, b2, b3, k0, lds, slot);
+      __builtin_amdgcn_sched_barrier(0);
+      aes_round(a0, a1, a2, a3, k1, lds, slot);
+      aes_round(b0, b1, b2, b3, k1, lds, slot);
+      __builtin_amdgcn_sched_barrier(0);
     }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  const uint4 kl = ldk4(rk + 4 * nr);
-  if (W) {
-    aes_last2w(a0, a1, a2, a3, b0, b1, b2, b3, kl, lds, slot, ka, kb);
-  } else {
+    const uint4 k0 = ldk4(rk + 4 * nr - 4), kl = ldk4(rk + 4 * nr);
+    if (!(gopts() & 4)) {
+      aes_round(a0, a1, a2, a3, k0, lds, slot);
+      aes_round(b0, b1, b2, b3, k0, lds, slot);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     ka = aes_last(a0, a1, a2, a3, kl, lds, slot);
     kb = aes_last(b0, b1, b2, b3, kl, lds, slot);
+    return;
   }
+  // lone wave: all 32 lookups of a round are issued before it waits
+#pragma unroll 1
+  for (int r = 3; r < ((gopts() & 4) ? 3 : nr); ++r) {
+    aes_round2w(a0, a1, a2, a3, b0, b1, b2, b3, ldk4(rk + 4 * r), lds, slot);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  aes_last2w(a0, a1, a2, a3, b0, b1, b2, b3, ldk4(rk + 4 * nr), lds, slot, ka, kb);
 }
 
 // ---- GHASH multiply by a fixed power (gf_mul, gfmult.c:219-229) ----------
@@ -409,31 +427,40 @@ __device__ __forceinline__ GhLane gh_lane(int lane) {
   return g;
 }
 
+template <int G = 2>
 __device__ __forceinline__ uint4 gf_mul8(uint4 x, const uint8_t *lds, const GhLane &g) {
   // slot k <- word k ^ ((L >> 2) & 3)
   const uint32_t a0 = g.sw1 ? x.y : x.x, a1 = g.sw1 ? x.x : x.y;
   const uint32_t a2 = g.sw1 ? x.w : x.z, a3 = g.sw1 ? x.z : x.w;
   const uint32_t w[4] = {g.sw2 ? a2 : a0, g.sw2 ? a3 : a1, g.sw2 ? a0 : a2, g.sw2 ? a1 : a3};
   uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = 0;
+  // G reads are issued per wait, 16 / G LDS round trips per multiply.  The
+  // interior pair steps take G = 4: there the AES state and its temporaries
+  // are dead, so a group's 16 result registers are free (in the general
+  // steps four per wait spilled 2-4 VGPRs).
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    // byte b of c = byte b ^ (L & 3) of slot k: position p = (4k + b) ^ (L & 15)
-    const uint32_t c = perm(w[k], w[k], g.selb);
-    const uint32_t cp = g.cpos0 ^ ((uint32_t)k * 0x40404040u);    // p << 4, bytes 0..3
+  for (int t0 = 0; t0 < 16; t0 += G) {
+    uint4 e[G];
 #pragma unroll
-    for (int b = 0; b < 4; b += 2) {
+    for (int q = 0; q < G; ++q) {
+      const int k = (t0 + q) >> 2, b = (t0 + q) & 3;
+      // byte b of c = byte b ^ (L & 3) of slot k: position p = (4k + b) ^ (L & 15)
+      const uint32_t c = perm(w[k], w[k], g.selb);
+      const uint32_t cp = g.cpos0 ^ ((uint32_t)k * 0x40404040u);    // p << 4, bytes 0..3
       const uint32_t ea = perm(c, cp, 0x0c0c0000u | ((4u + b) << 8) | (uint32_t)b);
-      const uint32_t eb = perm(c, cp, 0x0c0c0000u | ((5u + b) << 8) | (uint32_t)(b + 1));
-      const uint4 e = *reinterpret_cast<const uint4 *>(lds + LDS_GT + ea);
-      const uint4 f = *reinterpret_cast<const uint4 *>(lds + LDS_GT + eb);
-      r0 = xor3(r0, e.x, f.x);
-      r1 = xor3(r1, e.y, f.y);
-      r2 = xor3(r2, e.z, f.z);
-      r3 = xor3(r3, e.w, f.w);
+      e[q] = *reinterpret_cast<const uint4 *>(lds + LDS_GT + ea);
+    }
+    if (G > 2) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int q = 0; q < G; q += 2) {
+      r0 = xor3(r0, e[q].x, e[q + 1].x);
+      r1 = xor3(r1, e[q].y, e[q + 1].y);
+      r2 = xor3(r2, e[q].z, e[q + 1].z);
+      r3 = xor3(r3, e[q].w, e[q + 1].w);
     }
     // Materialize the partial sums here: otherwise the XORs sink into the
     // caller's `if (m < M)` and all 16 rows (64 VGPRs) stay live -> spills.
-    asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));
+    if (G > 2 || (t0 & 2) != 0) asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3));
   }
   return make_uint4(r0, r1, r2, r3);
 }
@@ -689,6 +716,10 @@ __device__ __forceinline__ void do_group(const GcmParams &p, const uint8_t *lds,
   };
 
   uint4 Y = make_uint4(0, 0, 0, 0), EJ0 = make_uint4(0, 0, 0, 0);
+  // the exec mask of an interior pair step: the record's lanes, if it is valid
+  // (taken once, here: testing `valid` at each step instead spilled 2 VGPRs in
+  // the S = 8 in-place kernel)
+  const bool step_mask = valid != 0;
   // Aligned schedule (MODE 0 / 1, S = 4, every record of the wave with pad =
   // S - 1, i.e. nct + 1 a multiple of S, as 1500-byte packets are): the AES
   // work is decoupled from the GHASH positions.  GHASH is unchanged (block i
@@ -731,24 +762,32 @@ __device__ __forceinline__ void do_group(const GcmParams &p, const uint8_t *lds,
         // interior: both slots full ciphertext blocks for every record
         if ((int)(ca >> 8) != cc.hi) ctr_cache_build(cc, s0c, s1c, s2c, (int)(ca >> 8), rk, lds, slot);
         if (__all((int)(cb >> 8) == cc.hi)) {
-          uint4 Ca = make_uint4(0, 0, 0, 0), Cb = make_uint4(0, 0, 0, 0);
-          if (valid && !(gopts() & 17)) {
-            Ca = ld16(rec + 16 + 16 * ja);
-            Cb = ld16(rec + 16 + 16 * jb);
+          // The whole step runs under the record's exec mask (an invalid
+          // record's Y and prev are never used).  Split into `if (valid)`
+          // regions around the AES rounds, the decrypt modes' GHASH reads of
+          // Ca and Cb came after a control-flow join at which the loads had
+          // to be assumed pending, and the wait placed there (vmcnt counts in
+          // order) waited for the step's two stores before the next loads.
+          if (step_mask) {
+            uint4 Ca = make_uint4(0, 0, 0, 0), Cb = make_uint4(0, 0, 0, 0);
+            if (valid && !(gopts() & 17)) {
+              Ca = ld16(rec + 16 + 16 * ja);
+              Cb = ld16(rec + 16 + 16 * jb);
+            }
+            uint4 ka, kb;
+            aes_ctr2(cc, ca, cb, rk3, nr, rk, lds, slot, ka, kb);
+            const uint4 Oa = xor4(Ca, ka), Ob = xor4(Cb, kb);
+            if (valid && !(gopts() & 9)) {
+              st16(orec + 16 + 16 * ja, Oa);
+              st16(orec + 16 + 16 * jb, Ob);
+            }
+            const uint4 Ba = MODE == 1 ? Oa : Ca;
+            if (gopts() & 2)
+              Y = xor4(xor4(Y, prev), Ba);
+            else
+              Y = xor4(gf_mul8<4>(xor4(gf_mul8<4>(Y, lds, gl), prev), lds, gl), Ba);
+            prev = MODE == 1 ? Ob : Cb;
           }
-          uint4 ka, kb;
-          aes_ctr2(cc, ca, cb, rk3, nr, rk, lds, slot, ka, kb);
-          const uint4 Oa = xor4(Ca, ka), Ob = xor4(Cb, kb);
-          if (valid && !(gopts() & 9)) {
-            st16(orec + 16 + 16 * ja, Oa);
-            st16(orec + 16 + 16 * jb, Ob);
-          }
-          const uint4 Ba = MODE == 1 ? Oa : Ca;
-          if (gopts() & 2)
-            Y = xor4(xor4(Y, prev), Ba);
-          else
-            Y = xor4(gf_mul8(xor4(gf_mul8(Y, lds, gl), prev), lds, gl), Ba);
-          prev = MODE == 1 ? Ob : Cb;
           continue;
         }
       }
@@ -795,26 +834,28 @@ __device__ __forceinline__ void do_group(const GcmParams &p, const uint8_t *lds,
         // stores are unconditional 16-byte accesses and GHASH takes them
         // unmasked.  Most pairs of a record take this path.
         if (__all(!valid || (i >= 1 && 16 * ib < ct_len))) {
-          uint4 Ca = make_uint4(0, 0, 0, 0), Cb = make_uint4(0, 0, 0, 0);
-          if (valid && !(gopts() & 17)) {
-            Ca = ld16(rec + 16 * i);
-            Cb = ld16(rec + 16 * ib);
+          if (step_mask) {                  // as in the aligned schedule
+            uint4 Ca = make_uint4(0, 0, 0, 0), Cb = make_uint4(0, 0, 0, 0);
+            if (valid && !(gopts() & 17)) {
+              Ca = ld16(rec + 16 * i);
+              Cb = ld16(rec + 16 * ib);
+            }
+            uint4 ka, kb;
+            aes_ctr2(cc, ca, cb, rk3, nr, rk, lds, slot, ka, kb);
+            uint4 Ba = Ca, Bb = Cb;
+            if (MODE == 1) {
+              Ba = xor4(Ca, ka);
+              Bb = xor4(Cb, kb);
+            }
+            if (valid && !(gopts() & 9)) {
+              st16(orec + 16 * i, MODE == 1 ? Ba : xor4(Ca, ka));
+              st16(orec + 16 * ib, MODE == 1 ? Bb : xor4(Cb, kb));
+            }
+            if (gopts() & 2)
+              Y = xor4(xor4(Y, Ba), Bb);
+            else
+              Y = xor4(gf_mul8<4>(xor4(gf_mul8<4>(Y, lds, gl), Ba), lds, gl), Bb);
           }
-          uint4 ka, kb;
-          aes_ctr2(cc, ca, cb, rk3, nr, rk, lds, slot, ka, kb);
-          uint4 Ba = Ca, Bb = Cb;
-          if (MODE == 1) {
-            Ba = xor4(Ca, ka);
-            Bb = xor4(Cb, kb);
-          }
-          if (valid && !(gopts() & 9)) {
-            st16(orec + 16 * i, MODE == 1 ? Ba : xor4(Ca, ka));
-            st16(orec + 16 * ib, MODE == 1 ? Bb : xor4(Cb, kb));
-          }
-          if (gopts() & 2)
-            Y = xor4(xor4(Y, Ba), Bb);
-          else
-            Y = xor4(gf_mul8(xor4(gf_mul8(Y, lds, gl), Ba), lds, gl), Bb);
           m += 2;
           continue;
         }
