@@ -1,0 +1,119 @@
+// decap.h — the inbound decapsulation rule (include/espgpu.h, the
+// decapsulation block): one function pair for espgpu_esp_decap on the host and
+// dcp_kernel on the device (decap.hip).
+//
+// Plain C++ with no HIP header, as classify.h, whose dword helpers it reuses:
+// the host side also builds with the host compiler alone
+// (tools/decap_selftest.cpp runs it under its sanitizers).
+#pragma once
+#include <stdint.h>
+
+#include "classify.h"
+
+namespace espgpu {
+
+constexpr uint32_t kInKnown = ESPGPU_IN_TRANSPORT | ESPGPU_IN_TUNNEL | ESPGPU_IN_PAD_RAND | ESPGPU_IN_AF6;
+
+// A dword of the packet in memory order, the counterpart of cls_ld32.
+ESPGPU_HD inline void dcp_st32(uint8_t *p, uint32_t v) {
+#ifdef __HIP_DEVICE_COMPILE__
+  *reinterpret_cast<uint32_t *>(p) = v;
+#else
+  p[0] = (uint8_t)v;
+  p[1] = (uint8_t)(v >> 8);
+  p[2] = (uint8_t)(v >> 16);
+  p[3] = (uint8_t)(v >> 24);
+#endif
+}
+
+// a 16-bit value as the big-endian field in one half of a memory-order dword
+ESPGPU_HD inline uint32_t dcp_be16(uint32_t x) { return ((x & 0xffu) << 8) | ((x >> 8) & 0xffu); }
+
+// What the rule decides without the packet: checks 1-3, and the result and
+// the booked bytes of checks 4 and 5.
+struct DecapPlan {
+  uint32_t transport;   // 1: the header moves (dcp_transport); 0: tunnel, nothing is touched
+  uint32_t off, len;    // the result, relative to the outer header
+  uint32_t nxt, q;
+};
+
+// Checks 1-3 of espgpu_esp_decap.  hlen = 8 + ivlen is the caller's.
+ESPGPU_HD inline int dcp_plan(uint32_t flags, uint32_t hlen, uint32_t alen, uint32_t skip, uint32_t rlen,
+                              uint32_t trailer, DecapPlan *p) {
+  const uint32_t mode = flags & (ESPGPU_IN_TRANSPORT | ESPGPU_IN_TUNNEL);
+  const bool af6 = flags & ESPGPU_IN_AF6;
+  if ((flags & ~kInKnown) || mode == (ESPGPU_IN_TRANSPORT | ESPGPU_IN_TUNNEL)) return ESPGPU_EINVAL;
+  if (skip & 3) return ESPGPU_EINVAL;
+  if (af6 ? skip != 40 : (skip < 20 || skip > 60)) return ESPGPU_EINVAL;
+  if ((uint64_t)rlen < (uint64_t)hlen + alen + 2) return ESPGPU_EINVAL;          // plen < 2
+  const uint32_t plen = rlen - hlen - alen;
+  if (!(trailer & ESPGPU_TR_VALID)) return ESPGPU_EINVAL;
+  if (trailer & ESPGPU_TR_BADLEN) return ESPGPU_EINVAL;                          // xform_esp.c:601-610
+  if ((trailer & ESPGPU_TR_BADPAD) && !(flags & ESPGPU_IN_PAD_RAND)) return ESPGPU_EINVAL;   // :613-623
+  if (trailer & ESPGPU_TR_NONE) return ESPGPU_ENODATA;                           // :629-630
+  const uint32_t nxt = trailer & 0xffu, padlen = (trailer >> 8) & 0xffu;
+  if (padlen + 2 > plen) return ESPGPU_EINVAL;       // a word that lacks the BADLEN it should carry
+  const uint32_t q = plen - padlen - 2;                                          // m_adj, :633
+  const bool inner4 = nxt == 4 && mode != ESPGPU_IN_TRANSPORT, inner6 = nxt == 41 && mode != ESPGPU_IN_TRANSPORT;
+  bool tunnel = false;
+  if (inner4 || inner6) {                            // ipsec_input.c:334-355, :539-562
+    if (q < (inner4 ? 20u : 40u)) return ESPGPU_EINVAL;
+    tunnel = true;
+  } else if (!af6 && mode == ESPGPU_IN_TUNNEL) {     // :411-416; ipsec6's protocol loop has no such end
+    return ESPGPU_EPFNOSUPPORT;
+  }
+  p->transport = !tunnel;
+  p->off = tunnel ? skip + hlen : hlen;
+  p->len = tunnel ? q : skip + q;
+  p->nxt = nxt;
+  p->q = q;
+  return 0;
+}
+
+// Check 5: the outer header's skip bytes from src to dst + hlen, fixed on the
+// way.  Every dword is loaded before the first is stored: with src == dst the
+// ranges overlap whenever hlen < skip.  The loops have constant bounds so that
+// the device keeps w[] in registers.
+ESPGPU_HD inline int dcp_transport(const uint8_t *src, uint8_t *dst, uint32_t flags, uint32_t hlen, uint32_t skip,
+                                   const DecapPlan &p) {
+  const uint32_t nw = skip / 4;                      // 5 .. 15
+  uint32_t w[15];
+#pragma unroll
+  for (uint32_t k = 0; k < 15; ++k) w[k] = k < nw ? cls_ld32(src + 4 * k) : 0u;
+  if (flags & ESPGPU_IN_AF6) {
+    if (((w[0] >> 4) & 0xfu) != 6) return ESPGPU_EINVAL;
+    // ip6_plen (ipsec_input.c:532), ip6_nxt (xform_esp.c:636); the hop limit stays
+    w[1] = (w[1] & 0xff000000u) | p.nxt << 16 | dcp_be16(p.q & 0xffffu);
+  } else {
+    if ((w[0] & 0xffu) != (0x40u | nw)) return ESPGPU_EINVAL;
+    w[0] = (w[0] & 0xffffu) | dcp_be16((skip + p.q) & 0xffffu) << 16;            // ip_len, :312
+    w[2] = (w[2] & 0x000000ffu) | p.nxt << 8;                                    // ip_p; ip_sum = 0, :313
+    // in_cksum over the header (:314): the one's-complement sum of the 16-bit
+    // words is the same in either byte order up to a byte swap, so the sum of
+    // the memory-order halves goes back into a memory-order half
+    uint64_t acc = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 15; ++k) acc += w[k];
+    acc = (acc & 0xffffffffu) + (acc >> 32);
+    acc = (acc & 0xffffu) + ((acc >> 16) & 0xffffu) + (acc >> 32);
+    acc = (acc & 0xffffu) + (acc >> 16);
+    acc = (acc & 0xffffu) + (acc >> 16);
+    w[2] |= (~(uint32_t)acc & 0xffffu) << 16;
+  }
+#pragma unroll
+  for (uint32_t k = 0; k < 15; ++k)
+    if (k < nw) dcp_st32(dst + hlen + 4 * k, w[k]);
+  return 0;
+}
+
+// espgpu_esp_decap's rule without the counters: status, and on 0 the result
+// in *p (p->len is also what the SA books: m_pkthdr.len at key_sa_recordxfer).
+ESPGPU_HD inline int esp_decap_rule(uint32_t flags, uint32_t ivlen, uint32_t alen, const uint8_t *src, uint8_t *dst,
+                                    uint32_t skip, uint32_t rlen, uint32_t trailer, DecapPlan *p) {
+  const uint32_t hlen = 8 + ivlen;
+  int st = dcp_plan(flags, hlen, alen, skip, rlen, trailer, p);
+  if (st == 0 && p->transport) st = dcp_transport(src, dst, flags, hlen, skip, *p);
+  return st;
+}
+
+}  // namespace espgpu

@@ -4,6 +4,7 @@
 #include "espgpu_ctx.h"
 
 #include "classify.h"      // (after the HIP runtime's vector types)
+#include "decap.h"
 
 namespace espgpu {
 namespace {
@@ -449,6 +450,43 @@ int espgpu_esp_classify_batch(espgpu_ctx *c, const uint8_t *d_arena, const espgp
   // no workspace and nothing of the ctx's is touched: the caller's stream orders it
   if (launch_esp_classify(d_arena, d_pkt, n, d_table, nslots, flags, d_desc, d_cstatus, stream))
     return batch_rc(c, fail(c, ESPGPU_EIO, "classify kernel launch failed"));
+  return 0;
+}
+
+// ---- inbound decapsulation ----------------------------------------------------
+// esp_input_cb's tail and ipsec4/6_common_input_cb for one packet.  The rule
+// espgpu_esp_decap_batch applies (decap.h).
+int espgpu_esp_decap(espgpu_insa *in, const espgpu_eshape *s, uint8_t *pkt, uint32_t skip, uint32_t rlen,
+                     uint32_t trailer, uint32_t *out_off, uint32_t *out_len) {
+  if (out_off) *out_off = 0;
+  if (out_len) *out_len = 0;
+  if (!in || !s || !pkt || !out_off || !out_len) return ESPGPU_EINVAL;
+  if ((s->ivlen != 0 && s->ivlen != 8 && s->ivlen != 16) || s->alen > 0xffffu) return ESPGPU_EINVAL;
+  DecapPlan p;
+  const int st = esp_decap_rule(in->flags, s->ivlen, s->alen, pkt, pkt, skip, rlen, trailer, &p);
+  if (st) return st;
+  *out_off = p.off;
+  *out_len = p.len;
+  in->bytes += p.len;                                            // key.c:8429-8445
+  in->packets += 1;
+  return 0;
+}
+
+int espgpu_esp_decap_batch(espgpu_ctx *c, const uint8_t *d_arena, uint8_t *d_out, const espgpu_pkt *d_pkt,
+                           const espgpu_desc *d_desc, const uint32_t *d_trailer, const uint8_t *d_status, uint32_t n,
+                           espgpu_insa *d_in, uint32_t nin, espgpu_pkt *d_ipkt, uint8_t *d_dstatus, void *stream) {
+  if (!c) return ESPGPU_EINVAL;
+  if (n && (!d_arena || !d_out || !d_pkt || !d_desc || !d_trailer || !d_status || !d_ipkt || !d_dstatus ||
+            (nin && !d_in) || ((uintptr_t)d_arena & 3) || ((uintptr_t)d_out & 3)))
+    return ESPGPU_EINVAL;
+  if (c->failed) return ESPGPU_EIO;
+  if (n == 0) return 0;
+  if (take_launch_fault(c)) return batch_rc(c, ESPGPU_EIO);
+  // no workspace; of the ctx only the session table is read, as the crypto
+  // kernels read it: the caller's stream orders it
+  if (launch_esp_decap(d_arena, d_out, d_pkt, d_desc, d_trailer, d_status, n, d_in, nin, c->d_sas,
+                       c->cfg.max_sessions, d_ipkt, d_dstatus, stream))
+    return batch_rc(c, fail(c, ESPGPU_EIO, "decap kernel launch failed"));
   return 0;
 }
 

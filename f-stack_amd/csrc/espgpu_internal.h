@@ -1,6 +1,6 @@
 // espgpu_internal.h — device-side data layouts shared by the host runtime
 // (espgpu*.cpp) and the HIP kernels (esp_gcm.hip, esp_cbc.hip, esp_ah.hip,
-// plan.hip, replay.hip, classify.hip, xfer.hip).
+// plan.hip, replay.hip, classify.hip, decap.hip, xfer.hip).
 #pragma once
 #include <stdint.h>
 
@@ -325,6 +325,11 @@ int launch_esp_frame(uint8_t *arena, espgpu_desc *desc, const uint32_t *frame, u
 // espgpu_esp_classify_batch (classify.hip; the rule is classify.h's)
 int launch_esp_classify(const uint8_t *arena, const espgpu_pkt *pkt, uint32_t n, const espgpu_sad_entry *table,
                         uint32_t nslots, uint32_t flags, espgpu_desc *desc, uint8_t *cstatus, void *stream);
+// espgpu_esp_decap_batch (decap.hip; the rule is decap.h's); nsas = the
+// capacity of the DevSA table
+int launch_esp_decap(const uint8_t *arena, uint8_t *out, const espgpu_pkt *pkt, const espgpu_desc *desc,
+                     const uint32_t *trailer, const uint8_t *status, uint32_t n, espgpu_insa *in, uint32_t nin,
+                     const DevSA *sas, uint32_t nsas, espgpu_pkt *ipkt, uint8_t *dstatus, void *stream);
 int launch_xfer(const XferSpan *spans, uint32_t nspans, const uint8_t *status, void *stream);
 int launch_replay_merge(uint8_t *status, const uint8_t *rstatus, uint32_t n, void *stream);
 int launch_plan(const espgpu_desc *d_desc, uint32_t n, const DevSA *sas, uint32_t nsas, uint32_t cap_sas,

@@ -7,6 +7,8 @@ import ctypes as C
 import os
 import re
 
+import numpy as np
+
 PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))   # f-stack_amd/
 LIB_PATH = os.environ.get("ESPGPU_LIB", os.path.join(PKG_ROOT, "libespgpu.so"))
 HEADER = os.path.join(os.path.dirname(PKG_ROOT), "include", "espgpu.h")
@@ -115,6 +117,17 @@ class SadEntry(C.Structure):
 CLS_IPCSUM, ENOENT, ENOTSUP = 0x1, 2, 95
 
 
+class InSA(C.Structure):
+    """struct espgpu_insa: one SA's inbound lifetime counters and ESPGPU_IN_* flags."""
+    _fields_ = [("bytes", C.c_uint64), ("packets", C.c_uint64), ("flags", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+# the same as a numpy record, for batch.esp_decap's insa tensor
+INSA_DTYPE = np.dtype([("bytes", "<u8"), ("packets", "<u8"), ("flags", "<u4"), ("pad_", "<u4")])
+IN_TRANSPORT, IN_TUNNEL, IN_PAD_RAND, IN_AF6 = 0x1, 0x2, 0x4, 0x8
+ENODATA, EPFNOSUPPORT = 61, 96
+
+
 class Config(C.Structure):
     _fields_ = [("device", C.c_int), ("max_sessions", C.c_uint32),
                 ("batch_records", C.c_uint32), ("batch_bytes", C.c_uint32),
@@ -188,6 +201,10 @@ def lib():
         L.espgpu_sad_build.argtypes = [vp, C.c_uint32, vp, C.c_uint32]
         L.espgpu_esp_classify.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(Desc)]
         L.espgpu_esp_classify_batch.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, vp, vp, vp]
+        if hasattr(L, "espgpu_esp_decap_batch"):        # (absent from older builds used in A/B runs)
+            L.espgpu_esp_decap.argtypes = [C.POINTER(InSA), C.POINTER(EShape), vp, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+            L.espgpu_esp_decap_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
         L.espgpu_last_kernel_ms.argtypes = [vp]
         L.espgpu_last_kernel_ms.restype = C.c_float
         L.espgpu_set_tuning.argtypes = [vp, C.c_char_p, C.c_int]

@@ -182,6 +182,34 @@ def esp_classify(driver, arena, pkt, n, table, desc, cstatus, flags=0, stream=No
         raise RuntimeError("espgpu_esp_classify_batch: %s (%d)" % (driver.last_error(), rc))
 
 
+INSA_DTYPE = L.INSA_DTYPE
+assert INSA_DTYPE.itemsize == 24
+
+
+def esp_decap(driver, arena, out, pkt, desc, trailer, status, n, insa, ipkt, dstatus, stream=None):
+    """Inbound decapsulation, the last step before the final replay_merge
+    (espgpu_esp_decap_batch): pkt and desc as esp_classify took and gave them,
+    trailer and status as decrypt_batch and the merges left them, insa a uint8
+    CUDA tensor of INSA_DTYPE records indexed by session id (it stays on the
+    device for the next batch).  A transport record's outer header is read
+    from arena and written, fixed, into out just before the plaintext (out
+    may be arena); a tunnel record's packet is not touched.  ipkt receives one
+    PKT_DTYPE record per packet, where the resulting packet starts and its
+    length (length 0 for a record that is refused or took no part), dstatus 0
+    / EINVAL / ENODATA / EPFNOSUPPORT for replay_merge, and every SA's bytes
+    and packets grow by what was accepted."""
+    for t in (arena, out, pkt, desc, trailer, status, insa, ipkt, dstatus):
+        assert t.is_cuda and t.is_contiguous()
+    assert trailer.element_size() == 4 and trailer.numel() >= n
+    assert pkt.numel() >= n * PKT_DTYPE.itemsize and ipkt.numel() * ipkt.element_size() >= n * PKT_DTYPE.itemsize
+    nin = insa.numel() * insa.element_size() // INSA_DTYPE.itemsize
+    rc = driver.lib.espgpu_esp_decap_batch(
+        driver.ctx, arena.data_ptr(), out.data_ptr(), pkt.data_ptr(), desc.data_ptr(), trailer.data_ptr(),
+        status.data_ptr(), n, insa.data_ptr(), nin, ipkt.data_ptr(), dstatus.data_ptr(), _stream_ptr(stream))
+    if rc:
+        raise RuntimeError("espgpu_esp_decap_batch: %s (%d)" % (driver.last_error(), rc))
+
+
 def replay_merge(driver, status, rstatus, n, stream=None):
     rc = driver.lib.espgpu_replay_merge(driver.ctx, status.data_ptr(), rstatus.data_ptr(), n,
                                         _stream_ptr(stream))

@@ -364,6 +364,92 @@ def esp_classify_host(table, pkt, off4=0, flags=0):
     return rc, (d.off4, d.len, d.sa, d.esn_hi, d.salt)
 
 
+IPSEC_MODE_ANY, IPSEC_MODE_TRANSPORT, IPSEC_MODE_TUNNEL = 0, 1, 2    # netipsec/ipsec.h
+IPPROTO_IPIP, IPPROTO_IPV6 = 4, 41
+
+
+def esp_input_decap(mode, af6, prand, ivlen, alen, packet_bytes, skip):
+    """What esp_input_cb does after the window update (xform_esp.c:581-648)
+    and ipsec4_common_input_cb / ipsec6_common_input_cb up to netisr_queue
+    (ipsec_input.c:298-417, :531-638) with one packet, on bytes: the outer IP
+    header of `skip` bytes and the decrypted ESP record behind it.  mode is
+    saidx.mode, af6 whether saidx.dst is AF_INET6, prand SADB_X_EXT_PRAND.
+    Returns (status, resulting packet bytes, bytes key_sa_recordxfer books),
+    (status, None, 0) for a packet that is dropped.  What the callers of these
+    functions guarantee is checked first, with EINVAL: skip as ip_input /
+    ip6_input leave it, at least the two trailer bytes of payload, and in
+    transport mode a header whose own length and version agree with skip."""
+    m = bytes(packet_bytes)
+    hlen = 8 + ivlen                                                 # sizeof(struct newesp) + ivlen, :585
+    if skip % 4 or (skip != 40 if af6 else not 20 <= skip <= 60):
+        return L.EINVAL, None, 0
+    if len(m) - skip - hlen - alen < 2:
+        return L.EINVAL, None, 0
+    m = m[:len(m) - alen]                                            # m_adj(m, -alen), :548
+    m = m[:skip] + m[skip + hlen:]                                   # m_striphdr(m, skip, hlen), :588
+    lastthree = m[len(m) - 3:]                                       # :598
+    if lastthree[1] + 2 > len(m) - skip:                             # :601
+        return L.EINVAL, None, 0
+    if not prand and lastthree[1] != lastthree[0] and lastthree[1] != 0:   # :613-614
+        return L.EINVAL, None, 0
+    if lastthree[2] == IPPROTO_NONE:                                 # :629
+        return L.ENODATA, None, 0
+    m = m[:len(m) - (lastthree[1] + 2)]                              # m_adj, :633
+    protoff = 6 if af6 else 9                                        # ip6_nxt / ip_p
+    m = m[:protoff] + lastthree[2:3] + m[protoff + 1:]               # m_copyback, :636
+    prot = lastthree[2]
+    if not af6:                                                      # ipsec4_common_input_cb
+        ip = bytearray(m[:skip])
+        ip[2:4] = struct.pack(">H", len(m) & 0xffff)                 # ip_len, :312
+        ip[10:12] = b"\0\0"                                          # :313
+        ip[10:12] = struct.pack(">H", in_cksum(bytes(ip)))           # :314
+        fixed = bytes(ip) + m[skip:]
+        if prot == IPPROTO_IPIP and mode != IPSEC_MODE_TRANSPORT:    # :334-343
+            if len(m) - skip < 20:
+                return L.EINVAL, None, 0
+            fixed = fixed[skip:]                                     # m_striphdr(m, 0, ip_hl << 2)
+        elif prot == IPPROTO_IPV6 and mode != IPSEC_MODE_TRANSPORT:  # :346-355
+            if len(m) - skip < 40:
+                return L.EINVAL, None, 0
+            fixed = fixed[skip:]
+        else:
+            if prot != IPPROTO_IPV6 and mode == IPSEC_MODE_ANY:      # :357-365
+                prot = IPPROTO_IPIP
+            if mode == IPSEC_MODE_TRANSPORT:                         # :395-396
+                prot = IPPROTO_IPIP
+            if prot != IPPROTO_IPIP:                                 # :400-417
+                return L.EPFNOSUPPORT, None, 0
+            if m[0] != 0x40 | skip >> 2:                             # ip_input's, for the header in_cksum read
+                return L.EINVAL, None, 0
+        return 0, fixed, len(fixed)                                  # key_sa_recordxfer, :389
+    ip6 = bytearray(m[:40])                                          # ipsec6_common_input_cb
+    ip6[4:6] = struct.pack(">H", (len(m) - 40) & 0xffff)             # ip6_plen, :532
+    fixed = bytes(ip6) + m[40:]
+    if prot == IPPROTO_IPV6 and mode != IPSEC_MODE_TRANSPORT:        # :539-549
+        if len(m) - skip < 40:
+            return L.EINVAL, None, 0
+        fixed = fixed[skip:]
+    elif prot == IPPROTO_IPIP and mode != IPSEC_MODE_TRANSPORT:      # :552-562
+        if len(m) - skip < 20:
+            return L.EINVAL, None, 0
+        fixed = fixed[skip:]
+    elif m[0] >> 4 != 6:                                             # ip6_input's
+        return L.EINVAL, None, 0
+    return 0, fixed, len(fixed)                                      # :590; the protocol loop goes on in place
+
+
+def esp_decap_host(insa, shape, buf, skip, rlen, trailer, at=0):
+    """espgpu_esp_decap, the engine's host rule, on a bytearray that holds the
+    outer header at `at` and the decrypted record behind it, and an L.InSA:
+    returns (status, out_off, out_len)."""
+    import ctypes as C
+    raw = (C.c_uint8 * (len(buf) - at)).from_buffer(buf, at)
+    off, ln = C.c_uint32(0xdddddddd), C.c_uint32(0xdddddddd)
+    rc = L.lib().espgpu_esp_decap(C.byref(insa), C.byref(shape), C.cast(raw, C.c_void_p), skip, rlen, trailer,
+                                  C.byref(off), C.byref(ln))
+    return rc, off.value, ln.value
+
+
 def trailer_word(plain_payload):
     """The 32-bit word the kernels' fused trailer check produces for a
     decrypted payload (espgpu_decrypt_batch_trailer, include/espgpu.h):

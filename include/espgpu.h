@@ -367,6 +367,11 @@ int  espgpu_decrypt_host(espgpu_ctx *ctx, const uint8_t *h_arena, uint64_t arena
  *   3. espgpu_replay_update_batch  ipsec_updatereplay for what authenticated
  *   4. espgpu_replay_merge, once with 1's and once with 3's result, and a
  *      third time with 0's: espgpu_replay_merge(d_status, d_cstatus, n).
+ *   5. espgpu_esp_decap_batch      esp_input_cb's tail and ipsec4/6_common_
+ *                                  input_cb: trailer verdict, strip, header fix,
+ *                                  SA lifetime counters (the decapsulation block
+ *                                  below; reads d_status as 4 left it)
+ *   6. espgpu_replay_merge         with 5's: (d_status, d_dstatus, n).
  * espgpu_replay_update / _update64 are the same update on the host, one
  * record per call. */
 #define ESPGPU_REPLAY_ESN    0x1     /* SADB_X_SAFLAGS_ESN  */
@@ -611,6 +616,98 @@ int  espgpu_esp_classify_batch(espgpu_ctx *ctx, const uint8_t *d_arena,
                                const struct espgpu_sad_entry *d_table, uint32_t nslots,
                                uint32_t flags, struct espgpu_desc *d_desc,
                                uint8_t *d_cstatus, void *stream);
+
+/* ---- inbound decapsulation (esp_input_cb after the window update and
+ *      ipsec4_common_input_cb / ipsec6_common_input_cb up to netisr_queue:
+ *      freebsd/netipsec/xform_esp.c:581-648, ipsec_input.c:298-417, :531-566,
+ *      key_sa_recordxfer, key.c:8429-8445) ----
+ * Steps 5 and 6 of the inbound sequence (replay block above): from a decrypted
+ * record, its status and its trailer word to the packet the stack takes next.
+ * One SA's inbound state as those functions read and advance it; the entry at
+ * index `sa` belongs to the session with that id.  Left to the caller or the
+ * host stack: the NAT-T checksum adjustment (classification sends NAT-T to
+ * the host already), the hhooks / enc(4), ipsec_if_input, ip_input of the
+ * inner packet and the SPD check. */
+#define ESPGPU_IN_TRANSPORT 0x1   /* saidx.mode == IPSEC_MODE_TRANSPORT                      */
+#define ESPGPU_IN_TUNNEL    0x2   /* IPSEC_MODE_TUNNEL; neither bit: IPSEC_MODE_ANY; both: unusable */
+#define ESPGPU_IN_PAD_RAND  0x4   /* SADB_X_EXT_PRAND: ESPGPU_TR_BADPAD is ignored (:613)    */
+#define ESPGPU_IN_AF6       0x8   /* saidx.dst is AF_INET6 (esp_input_cb picks the callback
+                                     by the SA's family, :638-648); clear: AF_INET           */
+#define ESPGPU_ENODATA      61    /* next header IPPROTO_NONE: RFC 4303 2.6 dummy, dropped   */
+#define ESPGPU_EPFNOSUPPORT 96    /* ipsec4_common_input_cb: "cannot handle inner ip proto"  */
+struct espgpu_insa {              /* 24 B, indexed by session id, lives in device memory     */
+	uint64_t bytes;               /* lft_c_bytes                                             */
+	uint64_t packets;             /* lft_c_allocations                                       */
+	uint32_t flags;               /* ESPGPU_IN_*                                             */
+	uint32_t pad_;
+};
+/* Host: decapsulate one packet of SA `in`.  `pkt` points at the outer IP
+ * header (`skip` bytes), the decrypted record lies at pkt + skip and is rlen
+ * bytes long, `shape` is the session's (hlen = 8 + ivlen, alen; blks is not
+ * read) and `trailer` the word espgpu_decrypt_batch_trailer gave for the
+ * record.  With plen = rlen - hlen - alen, padlen and nxt from the trailer
+ * word and q = plen - padlen - 2, the checks in order; the first that fires
+ * decides, and a refused packet has nothing written, books nothing and gets
+ * *out_off = *out_len = 0:
+ *   1. flags with unknown bits or both mode bits                     EINVAL
+ *      skip & 3; skip not in 20..60 (AF_INET) or not 40 (AF6)        EINVAL
+ *      plen < 2 (also ivlen not 0, 8 or 16)                          EINVAL
+ *      the trailer word without ESPGPU_TR_VALID                      EINVAL
+ *      ESPGPU_TR_BADLEN (xform_esp.c:601, esps_badilen)              EINVAL
+ *      ESPGPU_TR_BADPAD without ESPGPU_IN_PAD_RAND (:613-614)        EINVAL
+ *      ESPGPU_TR_NONE (:629)                                         ENODATA
+ *   2. AF_INET SA (ipsec_input.c:333-365, :395-417):
+ *      nxt 4 and not TRANSPORT: q < 20 EINVAL (:336), else tunnel (:342)
+ *      nxt 41 and not TRANSPORT: q < 40 EINVAL (:348), else tunnel (:354)
+ *      else TRANSPORT or ANY: transport (:357-365, :395-396)
+ *      else (TUNNEL, any other nxt)                                  EPFNOSUPPORT (:411-416)
+ *   3. AF6 SA (:538-566):
+ *      nxt 41 and not TRANSPORT: q < 40 EINVAL (:541), else tunnel (:547)
+ *      nxt 4 and not TRANSPORT: q < 20 EINVAL (:554), else tunnel (:560)
+ *      else transport: the protocol loop takes the packet in place (:564-566, :639-646)
+ *   4. tunnel: the packet is neither read nor written; the result is
+ *      {skip + hlen, q} and the SA books q bytes (m_pkthdr.len after :342 / :547).
+ *   5. transport: the outer header's skip bytes move forward by hlen, to end
+ *      where the plaintext starts (m_striphdr, xform_esp.c:588).
+ *      IPv4: ip_hl * 4 != skip or version nibble not 4               EINVAL
+ *        ip_len = skip + q (ipsec_input.c:312), ip_p = nxt (xform_esp.c:636),
+ *        ip_sum zeroed and recomputed over skip bytes as in_cksum does
+ *        (:313-314), never updated incrementally.
+ *      IPv6: version nibble not 6                                    EINVAL
+ *        ip6_plen = q (:532), ip6_nxt = nxt (xform_esp.c:636).
+ *      Every header byte is loaded before any is stored (the two ranges
+ *      overlap whenever hlen < skip).  The result is {hlen, skip + q} and the
+ *      SA books skip + q bytes.  [pkt, pkt + hlen), the padding, the trailer
+ *      and the ICV stay as they are (m_adj only shortens, :633).
+ *   6. accepted: in->bytes += booked, in->packets += 1 (key.c:8429-8445).
+ * *out_off is relative to pkt, *out_len the new m_pkthdr.len.  Null pointers
+ * are EINVAL. */
+int  espgpu_esp_decap(struct espgpu_insa *in, const struct espgpu_eshape *shape,
+                      uint8_t *pkt, uint32_t skip, uint32_t rlen, uint32_t trailer,
+                      uint32_t *out_off, uint32_t *out_len);
+/* The same rule for a device-resident batch, after the merges of the check's
+ * and the update's results into d_status.  Record i takes part if d_status[i]
+ * == 0, d_desc[i].sa < nin and the ctx holds an ESP session with that id (as
+ * espgpu_esp_frame_batch: not a DIGEST session, not a free slot); its shape
+ * is that session's, skip = (d_desc[i].off4 - d_pkt[i].off4) * 4 and rlen =
+ * d_desc[i].len.  The header is read from d_arena and written into d_out,
+ * where the decrypt put the plaintext; d_out == d_arena is the in-place form,
+ * otherwise d_arena is not written.  d_dstatus[i] is the rule's status and
+ * d_ipkt[i] = {d_pkt[i].off4 + out_off / 4, out_len}: absolute, so the array
+ * can be given to espgpu_esp_classify_batch for nested ESP.  A record with
+ * d_status[i] != 0 gets d_dstatus[i] = 0 and d_ipkt[i] = {d_pkt[i].off4, 0};
+ * one with status 0 that cannot take part gets EINVAL and the same empty
+ * d_ipkt[i].  When the work completes every d_in[sa] holds the sums of its
+ * accepted records (order-free: summed per wave, and per workgroup where one
+ * SA has all of it, before the 64-bit adds; never one add per record).  Both
+ * buffers are 4-byte aligned (EINVAL otherwise).  Asynchronous on the
+ * caller's stream, no workspace, no host round trip; n == 0 is a no-op that
+ * returns 0. */
+int  espgpu_esp_decap_batch(espgpu_ctx *ctx, const uint8_t *d_arena, uint8_t *d_out,
+                            const struct espgpu_pkt *d_pkt, const struct espgpu_desc *d_desc,
+                            const uint32_t *d_trailer, const uint8_t *d_status, uint32_t n,
+                            struct espgpu_insa *d_in, uint32_t nin,
+                            struct espgpu_pkt *d_ipkt, uint8_t *d_dstatus, void *stream);
 
 /* Device time of the last timed batch's crypto kernels (ms, from HIP events
  * on the batch stream).  Process-path batches of <= 128 KiB (a burst on its
