@@ -9,12 +9,7 @@
 #include <string.h>
 
 #include "espgpu.h"
-
-#if defined(__HIPCC__)
-#define ESPGPU_HD __host__ __device__
-#else
-#define ESPGPU_HD
-#endif
+#include "rule_hd.h"
 
 namespace espgpu {
 
@@ -24,17 +19,6 @@ ESPGPU_HD inline uint32_t key_u32hash(uint32_t spi) {
   uint32_t h = 33554467u;                              // FNV1_32_INIT
   for (int s = 24; s >= 0; s -= 8) h = (h * 0x01000193u) ^ ((spi >> s) & 0xffu);
   return h;
-}
-
-// A dword of the packet in memory order (byte k in bits 8k..8k+7).  The device
-// reads it whole: the header is 4-byte aligned by off4.  The host takes it
-// byte by byte, from wherever the caller's buffer starts.
-ESPGPU_HD inline uint32_t cls_ld32(const uint8_t *p) {
-#ifdef __HIP_DEVICE_COMPILE__
-  return *reinterpret_cast<const uint32_t *>(p);
-#else
-  return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-#endif
 }
 
 ESPGPU_HD inline uint32_t cls_bswap32(uint32_t x) { return __builtin_bswap32(x); }
@@ -84,7 +68,7 @@ ESPGPU_HD inline bool cls_lookup(const espgpu_sad_entry *table, uint32_t nslots,
     if (h.ids >> 16 != (50u | af << 8)) return false;
     const uint8_t *ed = table[slot].dst;
     for (uint32_t j = 0; j < (af == 4 ? 1u : 4u); ++j)
-      if (cls_ld32(ed + 4 * j) != dst[j]) return false;
+      if (mem_ld32(ed + 4 * j) != dst[j]) return false;
     *sa = h.ids & 0xffffu;
     *salt = h.salt;
     return true;
@@ -101,8 +85,8 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
   do {
     if (len < 20) break;
     // the 20 bytes every packet has, in one round of loads
-    const uint32_t w0 = cls_ld32(pkt), w1 = cls_ld32(pkt + 4), w2 = cls_ld32(pkt + 8), w3 = cls_ld32(pkt + 12),
-                   w4 = cls_ld32(pkt + 16);
+    const uint32_t w0 = mem_ld32(pkt), w1 = mem_ld32(pkt + 4), w2 = mem_ld32(pkt + 8), w3 = mem_ld32(pkt + 12),
+                   w4 = mem_ld32(pkt + 16);
     const uint32_t ver = (w0 >> 4) & 0xfu;
     if (ver == 4) {                                    // ip_input.c:488-561
       const uint32_t ihl = w0 & 0xfu, hlen = ihl * 4;
@@ -111,7 +95,7 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
         // one's-complement sum of the 16-bit words: the same in either byte
         // order up to a byte swap, and 0xffff is its own swap (in_cksum)
         uint64_t acc = (uint64_t)w0 + w1 + w2 + w3 + w4;
-        for (uint32_t k = 5; k < ihl; ++k) acc += cls_ld32(pkt + 4 * k);
+        for (uint32_t k = 5; k < ihl; ++k) acc += mem_ld32(pkt + 4 * k);
         acc = (acc & 0xffffffffu) + (acc >> 32);
         acc = (acc & 0xffffu) + ((acc >> 16) & 0xffffu) + (acc >> 32);
         acc = (acc & 0xffffu) + (acc >> 16);
@@ -139,7 +123,7 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
       if (40 + plen > len) break;
       st = ESPGPU_ENOTSUP;
       if (((w1 >> 16) & 0xffu) != 50) break;           // ip6_nxt
-      for (uint32_t j = 0; j < 4; ++j) dst[j] = cls_ld32(pkt + 24 + 4 * j);
+      for (uint32_t j = 0; j < 4; ++j) dst[j] = mem_ld32(pkt + 24 + 4 * j);
       if ((dst[0] & 0xc0ffu) == 0x80feu) break;        // fe80::/10
       st = ESPGPU_EINVAL;
       if (plen < 8 || (plen & 3)) break;
@@ -149,7 +133,7 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
     } else {
       break;
     }
-    spi = cls_bswap32(cls_ld32(pkt + skip));
+    spi = cls_bswap32(mem_ld32(pkt + skip));
     st = cls_lookup(table, nslots, spi, af, dst, &sa, &salt) ? 0 : ESPGPU_ENOENT;
   } while (0);
   espgpu_desc d;

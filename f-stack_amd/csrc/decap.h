@@ -2,29 +2,18 @@
 // decapsulation block): one function pair for espgpu_esp_decap on the host and
 // dcp_kernel on the device (decap.hip).
 //
-// Plain C++ with no HIP header, as classify.h, whose dword helpers it reuses:
-// the host side also builds with the host compiler alone
-// (tools/decap_selftest.cpp runs it under its sanitizers).
+// Plain C++ with no HIP header, as classify.h: the host side also builds with
+// the host compiler alone (tools/decap_selftest.cpp runs it under its
+// sanitizers).
 #pragma once
 #include <stdint.h>
 
-#include "classify.h"
+#include "espgpu.h"
+#include "rule_hd.h"
 
 namespace espgpu {
 
 constexpr uint32_t kInKnown = ESPGPU_IN_TRANSPORT | ESPGPU_IN_TUNNEL | ESPGPU_IN_PAD_RAND | ESPGPU_IN_AF6;
-
-// A dword of the packet in memory order, the counterpart of cls_ld32.
-ESPGPU_HD inline void dcp_st32(uint8_t *p, uint32_t v) {
-#ifdef __HIP_DEVICE_COMPILE__
-  *reinterpret_cast<uint32_t *>(p) = v;
-#else
-  p[0] = (uint8_t)v;
-  p[1] = (uint8_t)(v >> 8);
-  p[2] = (uint8_t)(v >> 16);
-  p[3] = (uint8_t)(v >> 24);
-#endif
-}
 
 // a 16-bit value as the big-endian field in one half of a memory-order dword
 ESPGPU_HD inline uint32_t dcp_be16(uint32_t x) { return ((x & 0xffu) << 8) | ((x >> 8) & 0xffu); }
@@ -79,7 +68,7 @@ ESPGPU_HD inline int dcp_transport(const uint8_t *src, uint8_t *dst, uint32_t fl
   const uint32_t nw = skip / 4;                      // 5 .. 15
   uint32_t w[15];
 #pragma unroll
-  for (uint32_t k = 0; k < 15; ++k) w[k] = k < nw ? cls_ld32(src + 4 * k) : 0u;
+  for (uint32_t k = 0; k < 15; ++k) w[k] = k < nw ? mem_ld32(src + 4 * k) : 0u;
   if (flags & ESPGPU_IN_AF6) {
     if (((w[0] >> 4) & 0xfu) != 6) return ESPGPU_EINVAL;
     // ip6_plen (ipsec_input.c:532), ip6_nxt (xform_esp.c:636); the hop limit stays
@@ -102,7 +91,7 @@ ESPGPU_HD inline int dcp_transport(const uint8_t *src, uint8_t *dst, uint32_t fl
   }
 #pragma unroll
   for (uint32_t k = 0; k < 15; ++k)
-    if (k < nw) dcp_st32(dst + hlen + 4 * k, w[k]);
+    if (k < nw) mem_st32(dst + hlen + 4 * k, w[k]);
   return 0;
 }
 

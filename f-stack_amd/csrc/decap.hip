@@ -25,7 +25,9 @@
 #include <hip/hip_runtime.h>
 
 #include "decap.h"
+#include "dev_prims.h"
 #include "espgpu_internal.h"
+#include "frame.h"
 
 namespace espgpu {
 
@@ -50,11 +52,6 @@ constexpr uint32_t kDcpNone = 0xfffffffeu, kDcpMixed = 0xffffffffu;   // a wave'
 __device__ __forceinline__ void dcp_book(espgpu_insa *in, uint32_t sa, uint32_t bytes, uint32_t count) {
   atomicAdd(reinterpret_cast<unsigned long long *>(&in[sa].bytes), (unsigned long long)bytes);
   atomicAdd(reinterpret_cast<unsigned long long *>(&in[sa].packets), (unsigned long long)count);
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x) {
-  for (uint32_t d = 32; d > 0; d >>= 1) x += __shfl_xor(x, d);
-  return x;
 }
 
 __global__ __launch_bounds__(256) void dcp_kernel(DcpArgs a) {

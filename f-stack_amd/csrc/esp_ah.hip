@@ -107,12 +107,6 @@ __device__ __forceinline__ void quad_recs(const uint8_t *rec, uint32_t n64, Quad
   qr.pn64[3] = qbcast<3>(n64);
 }
 
-__device__ __forceinline__ uint32_t wave_max(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o));
-  return v;
-}
-
 // HMAC-SHA1 / SHA2-256 of rec[0, L0) || be32(esn_hi)? for a whole wave (act =
 // this lane's record is hashed; every lane calls it; the block loop runs to
 // the wave's longest message).  [hlo, hhi): the hole (empty: hlo = hhi = 0).

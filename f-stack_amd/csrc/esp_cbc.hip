@@ -63,24 +63,6 @@ constexpr int CK_CTR = 1, CK_CBCMAC = 2;
 constexpr int CK_NARROW = -2, CK_WIDEH = -3;
 constexpr int kEtaU = 4;               // blocks per lane per pass of the block-parallel decrypt
 
-// first `rem` bytes (4, 8, 12 or >= 16) of v; no store shared with the full
-// path, so full blocks stay single 16-byte stores
-__device__ __forceinline__ void st_partial(uint8_t *p, uint4 v, int rem) {
-  if (rem >= 16) {
-    st16(p, v);
-    return;
-  }
-  if (rem > 4) {
-    V2a u = {v.x, v.y};
-    *reinterpret_cast<V2a *>(p) = u;
-  } else {
-    *reinterpret_cast<uint32_t *>(p) = v.x;
-  }
-  if (rem > 8) *reinterpret_cast<uint32_t *>(p + 8) = v.z;
-}
-__device__ __forceinline__ uint4 xor4(uint4 a, uint4 b) {
-  return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
-}
 __device__ __forceinline__ uint4 bswap4(uint4 v) {
   return make_uint4(bswap32(v.x), bswap32(v.y), bswap32(v.z), bswap32(v.w));
 }

@@ -48,6 +48,7 @@
 
 #include <algorithm>
 
+#include "dev_prims.h"
 #include "espgpu_internal.h"
 #include "xfer_copy.h"
 
@@ -73,54 +74,11 @@ struct __attribute__((aligned(4))) U4 {
   uint32_t x, y, z, w;
 };
 
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
-__device__ __forceinline__ uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) {
-  return __builtin_amdgcn_perm(hi, lo, sel);
-}
-__device__ __forceinline__ uint32_t ror16(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 16); }
-__device__ __forceinline__ uint32_t bswap32(uint32_t x) { return perm(x, x, 0x00010203u); }
-
-// 16- and 8-byte accesses at 4-byte alignment as single vector memory
-// operations (one IR access each, so the backend never splits or re-merges them)
-typedef uint32_t V4a __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint32_t V2a __attribute__((ext_vector_type(2), aligned(4)));
-// (nontemporal hints on these measured 4-14 % slower: DESIGN.md §6)
-__device__ __forceinline__ uint4 ld16(const uint8_t *p) {
-  const V4a v = *reinterpret_cast<const V4a *>(p);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void st16(uint8_t *p, uint4 v) {
-  V4a u = {v.x, v.y, v.z, v.w};
-  *reinterpret_cast<V4a *>(p) = u;
-}
-__device__ __forceinline__ void st8(uint8_t *p, uint32_t a, uint32_t b) {
-  V2a u = {a, b};
-  *reinterpret_cast<V2a *>(p) = u;
-}
-
 // Keep the first `rem` bytes of a 16-byte block, zero the rest.  Valid ESP
 // payloads are 4-byte multiples (the kernel rejects len % 4 != 0, as
 // esp_output pads to 4, xform_esp.c:710-716), so rem is 4, 8, 12 or >= 16.
 __device__ __forceinline__ uint4 mask_block(uint4 v, int rem) {
   return make_uint4(v.x, rem > 4 ? v.y : 0u, rem > 8 ? v.z : 0u, rem > 12 ? v.w : 0u);
-}
-
-// Store the first `rem` bytes (a multiple of 4) of v.
-__device__ __forceinline__ void st_partial(uint8_t *p, uint4 v, int rem) {
-  if (rem >= 16) {
-    st16(p, v);
-    return;
-  }
-  // the last block of a record: 4, 8 or 12 bytes, no store shared with the
-  // full-block path (a common first-word store would be hoisted out of both
-  // branches and split every full block into three stores)
-  if (rem > 4)
-    st8(p, v.x, v.y);
-  else
-    *reinterpret_cast<uint32_t *>(p) = v.x;
-  if (rem > 8) *reinterpret_cast<uint32_t *>(p + 8) = v.z;
 }
 
 // ---- AES (rijndaelEncrypt, rijndael-alg-fst.c:863-1042) on the pair table ----
@@ -534,9 +492,6 @@ __device__ __forceinline__ uint4 shfl_xor4(uint4 v, int m) {
 }
 __device__ __forceinline__ uint4 shfl4(uint4 v, int src) {
   return make_uint4(__shfl(v.x, src), __shfl(v.y, src), __shfl(v.z, src), __shfl(v.w, src));
-}
-__device__ __forceinline__ uint4 xor4(uint4 a, uint4 b) {
-  return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);
 }
 
 // The cold work of the chunk loop (session-change table staging, the first
@@ -1734,7 +1689,7 @@ int launch_gcm_door(const DoorArgs &a, int grid, void *stream) {
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-int launch_gcm(const GcmParams &pp, int encrypt, int two_pass, int grid, int lanes, void *stream) {
+int launch_gcm(const GcmParams &pp, int encrypt, int in_place, int grid, int lanes, void *stream) {
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (grid <= 0) grid = 256;
   constexpr int W = kGcmLanesSmall;
@@ -1751,7 +1706,7 @@ int launch_gcm(const GcmParams &pp, int encrypt, int two_pass, int grid, int lan
   // of kChunkRecs records (the grouping contract, include/espgpu.h).
   // burst kernel (small, E_K(J0) scratch given, out of place or encrypt):
   // chunks of one ctr wave's records, so a burst spreads over CUs
-  const bool burst = small && pp.ej0 != nullptr && !two_pass;
+  const bool burst = small && pp.ej0 != nullptr && !in_place;
   const uint32_t per = (pp.n + (uint32_t)grid - 1) / (uint32_t)grid;
   p.chunk = burst ? kBurstChunk : small ? 64 / W : 4 * (64 / kGcmLanesPerRec);
   while (p.chunk < per && p.chunk < (uint32_t)kChunkRecs) p.chunk <<= 1;
@@ -1770,7 +1725,7 @@ int launch_gcm(const GcmParams &pp, int encrypt, int two_pass, int grid, int lan
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
   if (p.xin != nullptr) {   // self-staging small batch (implicit chunks, S = 8, never in place)
-    if (p.chunks != nullptr || two_pass) return -1;
+    if (p.chunks != nullptr || in_place) return -1;
     if (encrypt)
       hipLaunchKernelGGL((gcm_kernel<1, 1024, W, true>), dim3(grid), dim3(1024), 0, st, p);
     else
@@ -1780,13 +1735,13 @@ int launch_gcm(const GcmParams &pp, int encrypt, int two_pass, int grid, int lan
   if (small) {
     if (encrypt)
       hipLaunchKernelGGL((gcm_kernel<1, 1024, W>), dim3(grid), dim3(1024), 0, st, p);
-    else if (two_pass)
+    else if (in_place)
       hipLaunchKernelGGL((gcm_kernel<kGcmInPlaceMode, 1024, W>), dim3(grid), dim3(1024), 0, st, p);
     else
       hipLaunchKernelGGL((gcm_kernel<0, 1024, W>), dim3(grid), dim3(1024), 0, st, p);
   } else if (encrypt) {
     hipLaunchKernelGGL((gcm_kernel<1, 1024, kGcmLanesPerRec>), dim3(grid), dim3(1024), 0, st, p);
-  } else if (two_pass) {
+  } else if (in_place) {
     hipLaunchKernelGGL((gcm_kernel<kGcmInPlaceMode, 1024, kGcmLanesPerRec>), dim3(grid), dim3(1024), 0, st, p);
   } else {
     hipLaunchKernelGGL((gcm_kernel<0, 1024, kGcmLanesPerRec>), dim3(grid), dim3(1024), 0, st, p);

@@ -748,7 +748,7 @@ void espgpu_fini(espgpu_ctx *c) {
   hipFree(c->d_queue);
   hipFree(c->d_ej0);
   hipFree(c->d_work); hipFree(c->d_order); hipFree(c->d_chunks); hipFree(c->d_nchunks);
-  hipFree(c->d_replay_ws);
+  hipFree(c->d_stage_ws);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
   if (c->ev_last) hipEventDestroy(c->ev_last);

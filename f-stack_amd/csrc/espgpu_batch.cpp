@@ -1,10 +1,13 @@
 // espgpu_batch.cpp — the kernel launches of the host runtime (espgpu_ctx.h):
-// run_batch, the device-resident batch entry points with the host-side
-// single-record rules beside them, and the host-to-host pipeline.
+// run_batch, the device-resident batch entry points with their single-record
+// counterparts beside them (the rules are classify.h's, decap.h's, frame.h's
+// and replay.h's), and the host-to-host pipeline.
 #include "espgpu_ctx.h"
 
 #include "classify.h"      // (after the HIP runtime's vector types)
 #include "decap.h"
+#include "frame.h"
+#include "replay.h"
 
 namespace espgpu {
 namespace {
@@ -29,7 +32,7 @@ int ensure_plan(espgpu_ctx *c, uint32_t n) {
 }
 
 // Around the launches that use what is per ctx (work-queue counters, planner
-// and replay workspaces): stream-ordered after the ctx's last launch, which
+// and stage workspaces): stream-ordered after the ctx's last launch, which
 // this one then becomes.
 int launch_begin(espgpu_ctx *c, hipStream_t st) {
   if (c->launched && st != c->last_st) HIPCHK(c, hipStreamWaitEvent(st, c->ev_last, 0));
@@ -97,13 +100,13 @@ int run_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32
     p.chunks = c->d_chunks;
     p.nchunks = c->d_nchunks;
   }
-  const int two_pass = (!encrypt && p.out == d_arena);
+  const int in_place = (!encrypt && p.out == d_arena);
   // E_K(J0) scratch: the burst kernel (small batches of <= gcm_burst records,
   // out of place or encrypt; launch_gcm picks the kernel from it)
   const bool gsmall = c->gcm_lanes ? c->gcm_lanes == kGcmLanesSmall : n < kGcmSmallBatch;
   // (packed output: the fused kernel only)
   if ((kinds & 1) && !out_stride &&
-      gsmall && !two_pass && n <= c->gcm_burst) {
+      gsmall && !in_place && n <= c->gcm_burst) {
     if (n > c->ej0_cap) {
       hipFree(c->d_ej0);
       c->d_ej0 = nullptr;
@@ -123,7 +126,7 @@ int run_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32
   // GCM records), but a few workgroups do: the others would only draw a
   // ticket past the end (cfg3: ~9 us -> ~3 us per batch)
   const int ggrid = c->n_gcm > 0 ? grid : std::min(grid, 16);
-  if ((kinds & 1) && launch_gcm(p, encrypt, two_pass, ggrid, c->gcm_lanes, st))
+  if ((kinds & 1) && launch_gcm(p, encrypt, in_place, ggrid, c->gcm_lanes, st))
     return fail(c, ESPGPU_EIO, "GCM kernel launch failed");
   if ((kinds & 2) && c->n_eta > 0) {
     EtaParams q{};
@@ -178,23 +181,38 @@ int batch_rc(espgpu_ctx *c, int e) {
   return e;
 }
 
-// The workspace grows with n and nreplay and is kept.  An allocation that
-// fails is ENOMEM with nothing launched and the ctx healthy.
-int ensure_replay_ws(espgpu_ctx *c, uint32_t n, uint32_t nreplay) {
-  if (c->d_replay_ws && n <= c->replay_ws_n && nreplay <= c->replay_ws_sas) return 0;
-  const uint32_t cap_n = std::max({n, c->replay_ws_n, 1024u}), cap_sas = std::max(nreplay, c->replay_ws_sas);
-  hipFree(c->d_replay_ws);               // (waits for the launches that use it)
-  c->d_replay_ws = nullptr;
-  c->replay_ws_n = c->replay_ws_sas = 0;
-  const size_t bytes = replay_update_workspace_bytes(cap_n, cap_sas);
-  if (hipMalloc(&c->d_replay_ws, bytes) != hipSuccess) {
+// The workspace of the stages that group by SA: it grows to the largest
+// request and is kept.  An allocation that fails is ENOMEM with nothing
+// launched and the ctx healthy.
+int ensure_stage_ws(espgpu_ctx *c, size_t bytes) {
+  if (c->d_stage_ws && bytes <= c->stage_ws_bytes) return 0;
+  hipFree(c->d_stage_ws);                // (waits for the launches that use it)
+  c->d_stage_ws = nullptr;
+  c->stage_ws_bytes = 0;
+  if (hipMalloc(&c->d_stage_ws, bytes) != hipSuccess) {
     (void)hipGetLastError();
-    c->d_replay_ws = nullptr;
+    c->d_stage_ws = nullptr;
     return fail(c, ESPGPU_ENOMEM, "replay update workspace: %zu bytes of device memory not available", bytes);
   }
-  c->replay_ws_n = cap_n;
-  c->replay_ws_sas = cap_sas;
+  c->stage_ws_bytes = bytes;
   return 0;
+}
+
+// What the device-resident stages share around their launches.  ws_bytes != 0:
+// the stage works in the ctx's workspace, so it is stream-ordered after the
+// ctx's last launch and becomes it; 0: nothing of the ctx's is written, the
+// caller's stream alone orders it.  `launch` returns nonzero if it could not
+// queue; `what` is then the message.
+template <class Launch>
+int run_stage(espgpu_ctx *c, uint32_t n, size_t ws_bytes, hipStream_t st, const char *what, Launch launch) {
+  if (c->failed) return ESPGPU_EIO;
+  if (n == 0) return 0;
+  int e = ws_bytes ? ensure_stage_ws(c, ws_bytes) : 0;
+  if (e) return e;
+  if (take_launch_fault(c)) return batch_rc(c, ESPGPU_EIO);
+  if (ws_bytes && (e = launch_begin(c, st))) return batch_rc(c, e);
+  if (launch()) return batch_rc(c, fail(c, ESPGPU_EIO, "%s", what));
+  return ws_bytes ? batch_rc(c, launch_end(c, st)) : 0;
 }
 
 int host_pipeline(espgpu_ctx *c, const uint8_t *h_arena, uint64_t arena_bytes,
@@ -249,12 +267,7 @@ using namespace espgpu;
 
 extern "C" {
 
-int espgpu_replay_params_ok(const espgpu_replay *r) {
-  if (!r) return 0;
-  if (r->wsize == 0) return 1;
-  const uint32_t b = r->bitmap_size;
-  return b != 0 && (b & (b - 1)) == 0 && (uint64_t)b * 32 >= (uint64_t)r->wsize * 8;
-}
+int espgpu_replay_params_ok(const espgpu_replay *r) { return r && replay_params_ok(*r); }
 
 int espgpu_replay_check_batch(espgpu_ctx *c, const uint8_t *d_arena, espgpu_desc *d_desc, uint32_t n,
                               const espgpu_replay *d_replay, uint32_t nreplay, const uint32_t *d_bitmap,
@@ -273,85 +286,15 @@ int espgpu_replay_merge(espgpu_ctx *c, uint8_t *d_status, const uint8_t *d_rstat
   return 0;
 }
 
-// ipsec_updatereplay (freebsd/netipsec/ipsec.c:1338-1436) with the window
-// helpers advance_window / set_window (:1203-1232): after authentication, in
-// arrival order per SA.
+// The single-record window updates; the rules are replay.h's.
 int espgpu_replay_update(espgpu_replay *r, uint32_t *bitmap, uint32_t seq) {
   if (!r || (r->wsize && !bitmap)) return ESPGPU_EINVAL;
-  if (r->wsize == 0) return 0;
-  // the window indexes the bitmap with bitmap_size - 1 as a mask: a power of
-  // two covering wsize * 8 bits (key.c:3346-3351 sizes it so)
-  if (!espgpu_replay_params_ok(r)) return ESPGPU_EINVAL;
-  if (seq == 0 && r->last == 0) return ESPGPU_EACCES;
-  uint32_t *bm = bitmap + r->bitmap_off;
-  const uint32_t mask = r->bitmap_size - 1;
-  auto seen = [&](uint32_t s) { return (bm[(s >> 5) & mask] >> (s & 31)) & 1u; };
-  auto mark = [&](uint32_t s) { bm[(s >> 5) & mask] |= 1u << (s & 31); };
-  auto advance = [&](uint64_t s) {      // clear the words the window top moves past
-    const uint64_t cur = r->last >> 5;
-    uint64_t diff = (s >> 5) - cur;
-    if (diff > r->bitmap_size) diff = r->bitmap_size;
-    for (uint64_t k = 0; k < diff; ++k) bm[(k + cur + 1) & mask] = 0;
-  };
-  const uint32_t window = r->wsize << 3;
-  const uint32_t tl = (uint32_t)r->last, th = (uint32_t)(r->last >> 32);
-  const uint32_t bl = tl - window + 1;
-  if ((tl >= window - 1 && seq >= bl) || (tl < window - 1 && seq < bl)) {
-    if (seq <= tl) {
-      if (seen(seq)) return ESPGPU_EACCES;
-      mark(seq);
-    } else {
-      const uint64_t s = ((uint64_t)th << 32) | seq;
-      advance(s);
-      mark(seq);
-      r->last = s;
-    }
-    return 0;
-  }
-  if (!(r->flags & ESPGPU_REPLAY_ESN)) return ESPGPU_EACCES;
-  if (tl < window - 1 && seq >= bl) {   // in the window, previous subspace
-    if (th == 0 || seen(seq)) return ESPGPU_EACCES;
-    mark(seq);
-    return 0;
-  }
-  if (th + 1 == 0) return ESPGPU_EACCES;   // the high part would wrap
-  const uint64_t s = ((uint64_t)(th + 1) << 32) | seq;
-  advance(s);
-  mark(seq);
-  r->last = s;
-  return 0;
+  return r->wsize == 0 ? 0 : replay_update_rule(r, bitmap, seq);
 }
 
-// The same update on the 64-bit sequence number the record was authenticated
-// under (ESN: esn_hi << 32 | seq; else seq): nothing is inferred, so a record
-// that has fallen below the window is refused, never taken for the next
-// subspace.  The rule espgpu_replay_update_batch applies (replay.hip).
 int espgpu_replay_update64(espgpu_replay *r, uint32_t *bitmap, uint64_t seq64) {
   if (!r || (r->wsize && !bitmap)) return ESPGPU_EINVAL;
-  if (r->wsize == 0) return 0;
-  const uint64_t window = (uint64_t)r->wsize << 3;
-  // as espgpu_replay_update, and the redundant block (key.c:3343-3351): a
-  // ring of at least window + 32 bits, or two sequence numbers of one window
-  // span could share a bit
-  if (!espgpu_replay_params_ok(r) || (uint64_t)r->bitmap_size * 32 < window + 32) return ESPGPU_EINVAL;
-  const uint64_t s = (r->flags & ESPGPU_REPLAY_ESN) ? seq64 : (uint32_t)seq64, top = r->last;
-  if (s == 0 && top == 0) return ESPGPU_EACCES;
-  uint32_t *bm = bitmap + r->bitmap_off;
-  const uint64_t mask = r->bitmap_size - 1;
-  uint32_t &word = bm[(s >> 5) & mask];
-  const uint32_t bit = 1u << (s & 31);
-  if (s > top) {
-    uint64_t diff = (s >> 5) - (top >> 5);          // clear the words the top moves past
-    if (diff > r->bitmap_size) diff = r->bitmap_size;
-    for (uint64_t k = 0; k < diff; ++k) bm[(k + (top >> 5) + 1) & mask] = 0;
-    word |= bit;
-    r->last = s;
-    return 0;
-  }
-  if (top - s >= window) return ESPGPU_EACCES;      // below the window
-  if (word & bit) return ESPGPU_EACCES;
-  word |= bit;
-  return 0;
+  return r->wsize == 0 ? 0 : replay_update64_rule(r, bitmap, seq64);
 }
 
 int espgpu_replay_update_batch(espgpu_ctx *c, const uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n,
@@ -359,17 +302,12 @@ int espgpu_replay_update_batch(espgpu_ctx *c, const uint8_t *d_arena, const espg
                                uint32_t *d_bitmap, uint8_t *d_ustatus, void *stream) {
   if (!c || (n && (!d_arena || !d_desc || !d_status || !d_ustatus || (nreplay && (!d_replay || !d_bitmap)))))
     return ESPGPU_EINVAL;
-  if (c->failed) return ESPGPU_EIO;
-  if (n == 0) return 0;
-  int e = ensure_replay_ws(c, n, nreplay);
-  if (e) return e;
-  if (take_launch_fault(c)) return batch_rc(c, ESPGPU_EIO);
-  // the workspace is per ctx, as the planner's: stream-ordered after the last launch
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if ((e = launch_begin(c, st))) return batch_rc(c, e);
-  if (launch_replay_update(d_arena, d_desc, n, d_status, d_replay, nreplay, d_bitmap, d_ustatus, c->d_replay_ws, st))
-    return batch_rc(c, fail(c, ESPGPU_EIO, "replay update launch failed"));
-  return batch_rc(c, launch_end(c, st));
+  return run_stage(c, n, replay_update_workspace_bytes(std::max(n, 1024u), nreplay), st,
+                   "replay update launch failed", [&] {
+                     return launch_replay_update(d_arena, d_desc, n, d_status, d_replay, nreplay, d_bitmap,
+                                                 d_ustatus, c->d_stage_ws, st);
+                   });
 }
 
 // ---- outbound framing ----------------------------------------------------------
@@ -386,38 +324,23 @@ int espgpu_esp_frame_shape(const espgpu_session_params *csp, uint32_t flags, esp
   return 0;
 }
 
-// esp_output between m_makespace and crypto_dispatch (xform_esp.c:703-716,
-// :782-887) for one record.  The rule espgpu_esp_frame_batch applies (replay.hip).
+// esp_output's framing of one record.  The rule espgpu_esp_frame_batch
+// applies (frame.h).
 int espgpu_esp_frame(espgpu_outsa *o, const espgpu_eshape *s, uint8_t *rec, uint32_t len, uint32_t rlen,
                      uint8_t next_header, uint32_t *esn_hi) {
   if (!o || !s || !rec || !esn_hi) return ESPGPU_EINVAL;
   if ((s->ivlen != 0 && s->ivlen != 8 && s->ivlen != 16) || (s->blks != 4 && s->blks != 16)) return ESPGPU_EINVAL;
-  if (rlen > 0xffffu || 8 + s->ivlen + rlen + esp_padding(rlen, s->blks) + s->alen != len) return ESPGPU_EINVAL;
-  if (esp_out_room(o->count, o->flags) == 0) return ESPGPU_EINVAL;
-  o->count++;                                                    // :793
-  const uint64_t cntr = o->cntr;
-  if (s->ivlen == 8) o->cntr++;                                  // :802-803
-  esp_frame_write(rec, *s, o->flags, o->spi, o->count, cntr, rlen, next_header);
-  *esn_hi = (o->flags & ESPGPU_OUT_ESN) ? (uint32_t)(o->count >> 32) : 0u;   // :799
-  return 0;
+  return esp_frame_rule(o, *s, rec, len, rlen, next_header, esn_hi);
 }
 
 int espgpu_esp_frame_batch(espgpu_ctx *c, uint8_t *d_arena, espgpu_desc *d_desc, const uint32_t *d_frame,
                            uint32_t n, espgpu_outsa *d_out, uint32_t nout, uint8_t *d_fstatus, void *stream) {
   if (!c || (n && (!d_arena || !d_desc || !d_frame || !d_fstatus || (nout && !d_out)))) return ESPGPU_EINVAL;
-  if (c->failed) return ESPGPU_EIO;
-  if (n == 0) return 0;
-  // the replay update's workspace holds this one's too (esp_frame_workspace_bytes)
-  int e = ensure_replay_ws(c, n, nout);
-  if (e) return e;
-  if (take_launch_fault(c)) return batch_rc(c, ESPGPU_EIO);
-  // the workspace is per ctx: stream-ordered after the last launch
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if ((e = launch_begin(c, st))) return batch_rc(c, e);
-  if (launch_esp_frame(d_arena, d_desc, d_frame, n, d_out, nout, c->d_sas, c->cfg.max_sessions, d_fstatus,
-                       c->d_replay_ws, st))
-    return batch_rc(c, fail(c, ESPGPU_EIO, "esp frame launch failed"));
-  return batch_rc(c, launch_end(c, st));
+  return run_stage(c, n, esp_frame_workspace_bytes(std::max(n, 1024u), nout), st, "esp frame launch failed", [&] {
+    return launch_esp_frame(d_arena, d_desc, d_frame, n, d_out, nout, c->d_sas, c->cfg.max_sessions, d_fstatus,
+                            c->d_stage_ws, st);
+  });
 }
 
 // ---- inbound classification ----------------------------------------------------
@@ -444,13 +367,10 @@ int espgpu_esp_classify_batch(espgpu_ctx *c, const uint8_t *d_arena, const espgp
   if (n && (!d_arena || !d_pkt || !d_table || !d_desc || !d_cstatus || nslots == 0 || (nslots & (nslots - 1)) ||
             ((uintptr_t)d_arena & 3) || ((uintptr_t)d_table & 15)))
     return ESPGPU_EINVAL;
-  if (c->failed) return ESPGPU_EIO;
-  if (n == 0) return 0;
-  if (take_launch_fault(c)) return batch_rc(c, ESPGPU_EIO);
-  // no workspace and nothing of the ctx's is touched: the caller's stream orders it
-  if (launch_esp_classify(d_arena, d_pkt, n, d_table, nslots, flags, d_desc, d_cstatus, stream))
-    return batch_rc(c, fail(c, ESPGPU_EIO, "classify kernel launch failed"));
-  return 0;
+  // no workspace and nothing of the ctx's is touched
+  return run_stage(c, n, 0, nullptr, "classify kernel launch failed", [&] {
+    return launch_esp_classify(d_arena, d_pkt, n, d_table, nslots, flags, d_desc, d_cstatus, stream);
+  });
 }
 
 // ---- inbound decapsulation ----------------------------------------------------
@@ -479,15 +399,12 @@ int espgpu_esp_decap_batch(espgpu_ctx *c, const uint8_t *d_arena, uint8_t *d_out
   if (n && (!d_arena || !d_out || !d_pkt || !d_desc || !d_trailer || !d_status || !d_ipkt || !d_dstatus ||
             (nin && !d_in) || ((uintptr_t)d_arena & 3) || ((uintptr_t)d_out & 3)))
     return ESPGPU_EINVAL;
-  if (c->failed) return ESPGPU_EIO;
-  if (n == 0) return 0;
-  if (take_launch_fault(c)) return batch_rc(c, ESPGPU_EIO);
   // no workspace; of the ctx only the session table is read, as the crypto
-  // kernels read it: the caller's stream orders it
-  if (launch_esp_decap(d_arena, d_out, d_pkt, d_desc, d_trailer, d_status, n, d_in, nin, c->d_sas,
-                       c->cfg.max_sessions, d_ipkt, d_dstatus, stream))
-    return batch_rc(c, fail(c, ESPGPU_EIO, "decap kernel launch failed"));
-  return 0;
+  // kernels read it
+  return run_stage(c, n, 0, nullptr, "decap kernel launch failed", [&] {
+    return launch_esp_decap(d_arena, d_out, d_pkt, d_desc, d_trailer, d_status, n, d_in, nin, c->d_sas,
+                            c->cfg.max_sessions, d_ipkt, d_dstatus, stream);
+  });
 }
 
 int espgpu_decrypt_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32_t n,

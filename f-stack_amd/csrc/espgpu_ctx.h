@@ -195,9 +195,10 @@ struct espgpu_ctx {
   uint32_t *d_work = nullptr, *d_order = nullptr, *d_nchunks = nullptr;
   espgpu::Chunk *d_chunks = nullptr;
   uint32_t max_chunks = 0;
-  // espgpu_replay_update_batch's workspace, grown to the largest (n, nreplay) seen
-  void *d_replay_ws = nullptr;
-  uint32_t replay_ws_n = 0, replay_ws_sas = 0;
+  // the workspace of the stages that group by SA (window update, framing),
+  // grown to the largest request seen
+  void *d_stage_ws = nullptr;
+  size_t stage_ws_bytes = 0;
   // staging
   std::vector<espgpu::Slot> slots;
   int cur = 0;

@@ -1,6 +1,7 @@
 // espgpu_internal.h — device-side data layouts shared by the host runtime
 // (espgpu*.cpp) and the HIP kernels (esp_gcm.hip, esp_cbc.hip, esp_ah.hip,
-// plan.hip, replay.hip, classify.hip, decap.hip, xfer.hip).
+// plan.hip, sa_group.hip, replay.hip, frame.hip, classify.hip, decap.hip,
+// xfer.hip).
 #pragma once
 #include <stdint.h>
 
@@ -226,7 +227,7 @@ struct DoorArgs {
 int launch_gcm_door(const DoorArgs &a, int grid, void *stream);
 // lanes: 0 = by batch size (kGcmLanesSmall below kGcmSmallBatch records,
 // else kGcmLanesPerRec), or force 4 / 8 (set_tuning "gcm_lanes", tests)
-int launch_gcm(const GcmParams &p, int encrypt, int two_pass, int grid, int lanes, void *stream);
+int launch_gcm(const GcmParams &p, int encrypt, int in_place, int grid, int lanes, void *stream);
 int set_gcm_opts(uint32_t opts);   // measurement knobs (`make knobs` builds only)
 int set_eta_opts(uint32_t opts);
 // kinds: bit 0 = SHA-1 / SHA2-256 / no-auth CBC sessions in the SA table,
@@ -245,80 +246,9 @@ size_t replay_update_workspace_bytes(uint32_t n, uint32_t nrp);
 int launch_replay_update(const uint8_t *arena, const espgpu_desc *desc, uint32_t n, const uint8_t *status,
                          espgpu_replay *rp, uint32_t nrp, uint32_t *bitmap, uint8_t *ustatus, void *ws,
                          void *stream);
-// ---- outbound framing (espgpu_esp_frame / _frame_batch) -----------------------
-// One rule for the host function and the kernels: the shape of a session, how
-// many numbers an SA may still give out, and the bytes of one framed record.
-// esp_output's hlen - 8, blks and alen (xform_esp.c:698-718) from what DevSA
-// keeps of a session; false for a free slot or a DIGEST session.
-__host__ __device__ inline bool esp_shape_of(uint32_t mode, uint32_t calg, uint32_t mlen, uint32_t oflags,
-                                   espgpu_eshape *s) {
-  if (mode == ESPGPU_CSP_MODE_AEAD) {
-    s->ivlen = 8;
-    s->blks = 4;
-  } else if (mode == ESPGPU_CSP_MODE_ETA && calg == ESPGPU_CRYPTO_AES_CBC) {
-    s->ivlen = 16;
-    s->blks = 16;
-  } else if (mode == ESPGPU_CSP_MODE_ETA && calg == ESPGPU_CRYPTO_AES_ICM) {
-    s->ivlen = 8;
-    s->blks = (oflags & ESPGPU_OUT_CTRCOMPAT) ? 16 : 4;   // native_blocksize, :710-711
-  } else if (mode == ESPGPU_CSP_MODE_ETA && calg == ESPGPU_CRYPTO_NULL_CBC) {
-    s->ivlen = 0;
-    s->blks = 4;
-  } else {
-    return false;
-  }
-  s->alen = mlen;
-  return true;
-}
-
-__host__ __device__ inline uint32_t esp_padding(uint32_t rlen, uint32_t blks) {
-  return ((blks - ((rlen + 2) % blks)) % blks) + 2;       // :716
-}
-
-// Sequence numbers the SA may still give out from `count`: ah_output's
-// condition (xform_ah.c:940-943) under WRAPCHECK, else no limit.
-__host__ __device__ inline uint64_t esp_out_room(uint64_t count, uint32_t oflags) {
-  if (!(oflags & ESPGPU_OUT_WRAPCHECK) || (oflags & ESPGPU_OUT_CYCSEQ)) return ~0ull;
-  return (oflags & ESPGPU_OUT_ESN) ? ~count : (uint64_t)(0xffffffffu - (uint32_t)count);
-}
-
-// The bytes esp_output writes into one record: header (:783-797), counter IV
-// (:875-881), padding and trailer (:824-839).  `count` is the record's
-// sequence number, `cntr` its explicit IV.  Every store lies inside the
-// record; the header dwords are whole (the record is 4-byte aligned on the
-// device), the padding starts at any byte and goes byte by byte.
-__host__ __device__ inline void esp_frame_write(uint8_t *rec, const espgpu_eshape &s, uint32_t oflags, uint32_t spi,
-                                      uint64_t count, uint64_t cntr, uint32_t rlen, uint8_t nh) {
-  auto put32 = [](uint8_t *p, uint32_t v) {
-#ifdef __HIP_DEVICE_COMPILE__
-    *reinterpret_cast<uint32_t *>(p) = __builtin_bswap32(v);
-#else
-    p[0] = (uint8_t)(v >> 24);
-    p[1] = (uint8_t)(v >> 16);
-    p[2] = (uint8_t)(v >> 8);
-    p[3] = (uint8_t)v;
-#endif
-  };
-  put32(rec, spi);
-  put32(rec + 4, (uint32_t)count);
-  if (s.ivlen == 8) {
-    put32(rec + 8, (uint32_t)(cntr >> 32));
-    put32(rec + 12, (uint32_t)cntr);
-  }
-  const uint32_t padding = esp_padding(rlen, s.blks);
-  uint8_t *pad = rec + 8 + s.ivlen + rlen;
-  if (oflags & ESPGPU_OUT_PAD_SEQ) {
-    for (uint32_t k = 0; k + 2 < padding; ++k) pad[k] = (uint8_t)(k + 1);
-  } else if (oflags & ESPGPU_OUT_PAD_ZERO) {
-    for (uint32_t k = 0; k + 2 < padding; ++k) pad[k] = 0;
-  }
-  pad[padding - 2] = (uint8_t)(padding - 2);
-  pad[padding - 1] = nh;
-}
-
-// espgpu_esp_frame_batch (replay.hip): ws = esp_frame_workspace_bytes(n, nout)
-// bytes, never more than replay_update_workspace_bytes(n, nout); nsas = the
-// capacity of the DevSA table.
+// espgpu_esp_frame_batch (frame.hip; the rule is frame.h's): ws =
+// esp_frame_workspace_bytes(n, nout) bytes of device memory (monotonic in
+// both); nsas = the capacity of the DevSA table.
 size_t esp_frame_workspace_bytes(uint32_t n, uint32_t nout);
 int launch_esp_frame(uint8_t *arena, espgpu_desc *desc, const uint32_t *frame, uint32_t n, espgpu_outsa *out,
                      uint32_t nout, const DevSA *sas, uint32_t nsas, uint8_t *fstatus, void *ws, void *stream);

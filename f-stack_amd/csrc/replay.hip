@@ -1,6 +1,7 @@
 // replay.hip — the ESP replay window for a device-resident batch: the
-// pre-filter before crypto and the window update after it; and, over the
-// same grouping by SA, the outbound framing before encrypt (at the end).
+// pre-filter before crypto and the window update after it.  The predicates
+// both share with the host rules are replay.h's; the grouping by SA that the
+// update is built on is sa_group.hip's.
 //
 // The inbound sequence on a batch (include/espgpu.h, replay block):
 //   1. espgpu_replay_check_batch  esp_input's ipsec_chkreplay (xform_esp.c:
@@ -30,27 +31,22 @@
 //   * the final window is last = the SA's maximum, the ring words between the
 //     initial and the final top zeroed, then the bit of every accepted record
 //     that is less than a ring below the final top.
-// So: a stable LSD radix sort of the records by SA (8-bit digits, as many
-// passes as the SA count needs), a segmented max-scan over the grouped
+// So: a stable LSD radix sort of the records by SA (sa_group.hip: 8-bit digits,
+// as many passes as the SA count needs), a segmented max-scan over the grouped
 // positions (three kernels, kReplayScanBlock positions per workgroup), a hash
 // table holding the first grouped position per (SA, seq64), the decisions
 // (which read the initial bitmap), then clear and set as two more launches.
 // Every step is a grid over records or over SAs, whatever the SA mix.
 #include <hip/hip_runtime.h>
 
+#include "dev_prims.h"
 #include "espgpu_internal.h"
+#include "replay.h"
+#include "sa_group.h"
 
 namespace espgpu {
 
 namespace {
-
-__device__ __forceinline__ uint32_t be32(uint32_t x) { return __builtin_amdgcn_perm(x, x, 0x00010203u); }
-
-// check_window (ipsec.c:1191-1201): bit (seq & 31) of word (seq >> 5) masked
-// by the power-of-two bitmap size (IPSEC_REDUNDANT_BIT_SHIFTS, :1177-1180).
-__device__ __forceinline__ bool seen(const espgpu_replay &r, const uint32_t *bitmap, uint32_t seq) {
-  return (bitmap[r.bitmap_off + ((seq >> 5) & (r.bitmap_size - 1))] >> (seq & 31)) & 1u;
-}
 
 // ipsec_chkreplay (ipsec.c:1248-1331): true = permitted, *seqhigh set.
 __device__ bool chkreplay(const espgpu_replay &r, const uint32_t *bitmap, uint32_t seq, uint32_t *seqhigh) {
@@ -62,7 +58,7 @@ __device__ bool chkreplay(const espgpu_replay &r, const uint32_t *bitmap, uint32
   // subspace, or in [0, bl) with the window spanning two
   if ((tl >= window - 1 && seq >= bl) || (tl < window - 1 && seq < bl)) {
     *seqhigh = th;
-    return !(seq <= tl && seen(r, bitmap, seq));
+    return !(seq <= tl && replay_seen(r, bitmap, seq));
   }
   // top of a non-ESN space reached: only SADB_X_EXT_CYCSEQ SAs go on
   if (tl == 0xffffffffu && !(r.flags & ESPGPU_REPLAY_ESN) && !(r.flags & ESPGPU_REPLAY_CYCSEQ))
@@ -70,7 +66,7 @@ __device__ bool chkreplay(const espgpu_replay &r, const uint32_t *bitmap, uint32
   if (tl < window - 1 && seq >= bl) {         // in the window, previous subspace
     if (th == 0) return false;
     *seqhigh = th - 1;
-    return !seen(r, bitmap, seq);
+    return !replay_seen(r, bitmap, seq);
   }
   *seqhigh = th + 1;                           // wrapped into the next subspace
   return !(th + 1 == 0 && !(r.flags & ESPGPU_REPLAY_CYCSEQ));
@@ -86,7 +82,7 @@ __global__ __launch_bounds__(256) void replay_check_kernel(const uint8_t *arena,
   if (d.sa < nrp && d.len >= 8) {
     const espgpu_replay r = rp[d.sa];
     if (r.wsize != 0) {                        // esp_input: replay != NULL && wsize != 0
-      const uint32_t seq = be32(*reinterpret_cast<const uint32_t *>(arena + (size_t)d.off4 * 4 + 4));
+      const uint32_t seq = bswap32(*reinterpret_cast<const uint32_t *>(arena + (size_t)d.off4 * 4 + 4));
       uint32_t seqh = 0;
       if (!chkreplay(r, bitmap, seq, &seqh)) {
         st = ESPGPU_EACCES;
@@ -106,23 +102,20 @@ __global__ __launch_bounds__(256) void replay_merge_kernel(uint8_t *status, cons
 
 // ---- window update ------------------------------------------------------------
 
-constexpr uint32_t kSortItems = 8;                 // records per thread of a sort tile
-constexpr uint32_t kSortTile = 256 * kSortItems;
 constexpr uint32_t kScanItems = kReplayScanBlock / 256;
 constexpr uint32_t kEmpty = 0xffffffffu;           // free hash slot (no grouped position is 2^32 - 1)
 
-// The workspace of one call, carved from the ctx's buffer (replay_update_carve).
+// The workspace of one call, carved from the ctx's buffer (upd_carve).
 struct UpdWs {
   uint64_t *sseq;          // [n] seq64 by grouped position (0 for records that take no part)
   uint64_t *top;           // [n] the window top each grouped position sees (M_i)
   uint64_t *agg_v, *car_v; // [scan blocks] segmented-scan aggregates and carries
   uint64_t *sa_top;        // [nsa] final top per SA (0: no record took part)
-  uint32_t *key[2], *idx[2];   // [n] sort buffers: SA (or nsa: takes no part), record index
+  GroupWs g;
   uint32_t *hash;          // [hcap] first grouped position per (SA, seq64)
-  uint32_t *counts;        // [256][sort tiles] digit histograms, then their exclusive scan
   uint32_t *agg_f, *car_f; // [scan blocks] segment-head flags of the aggregates / carries
   uint64_t hcap;
-  uint32_t sort_tiles, scan_blocks;
+  uint32_t scan_blocks;
 };
 
 struct UpdArgs {
@@ -133,7 +126,7 @@ struct UpdArgs {
   uint32_t *bitmap;
   uint8_t *ustatus;
   const uint32_t *skey, *order;   // the sorted buffers
-  uint32_t n, nrp, nsa;           // nsa = min(nrp, 65536): the key of a record that takes no part
+  uint32_t n, nrp, nsa;           // nsa = group_no_key(nrp)
   UpdWs w;
 };
 
@@ -141,11 +134,6 @@ __host__ __device__ inline uint64_t hash_cap(uint32_t n) {
   uint64_t c = 1024;
   while (c < 2 * (uint64_t)n) c <<= 1;
   return c;
-}
-
-__device__ __forceinline__ bool window_usable(const espgpu_replay &r) {
-  const uint32_t b = r.bitmap_size;
-  return b != 0 && (b & (b - 1)) == 0 && (uint64_t)b * 32 >= (uint64_t)r.wsize * 8 + 32;
 }
 
 // Which records take part, and under which SA.
@@ -158,108 +146,13 @@ __global__ __launch_bounds__(256) void upd_prep_kernel(UpdArgs a) {
   if (a.status[i] == 0 && d.sa < a.nrp && d.len >= 8) {
     const espgpu_replay r = a.rp[d.sa];
     if (r.wsize != 0) {
-      if (window_usable(r)) k = d.sa;
+      if (replay_usable64(r)) k = d.sa;
       else u = ESPGPU_EINVAL;
     }
   }
-  a.w.key[0][i] = k;
-  a.w.idx[0][i] = i;
+  a.w.g.key[0][i] = k;
+  a.w.g.idx[0][i] = i;
   a.ustatus[i] = u;
-}
-
-// One stable radix pass: digit histogram per tile, ...
-__global__ __launch_bounds__(256) void upd_hist_kernel(const uint32_t *key, uint32_t n, uint32_t shift,
-                                                       uint32_t *counts, uint32_t tiles) {
-  __shared__ uint32_t h[256];
-  const uint32_t tid = threadIdx.x;
-  h[tid] = 0;
-  __syncthreads();
-  const uint64_t base = (uint64_t)blockIdx.x * kSortTile;
-  for (uint32_t k = 0; k < kSortItems; ++k) {
-    const uint64_t e = base + k * 256 + tid;
-    if (e < n) atomicAdd(&h[(key[e] >> shift) & 255u], 1u);
-  }
-  __syncthreads();
-  counts[(size_t)tid * tiles + blockIdx.x] = h[tid];
-}
-
-__device__ __forceinline__ uint32_t wave_incl_add(uint32_t x, uint32_t lane) {
-  for (uint32_t d = 1; d < 64; d <<= 1) {
-    const uint32_t y = __shfl_up(x, d);
-    if (lane >= d) x += y;
-  }
-  return x;
-}
-
-// ... exclusive scan of the [digit][tile] counts (one workgroup: 256 x the
-// tile count is small beside n), ...
-__global__ __launch_bounds__(256) void upd_scan_counts_kernel(uint32_t *c, uint64_t m) {
-  __shared__ uint32_t wt[4];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  uint32_t carry = 0;
-  for (uint64_t base = 0; base < m; base += 2048) {
-    const uint64_t e0 = base + (uint64_t)tid * 8;
-    uint32_t x[8], sum = 0;
-    for (uint32_t j = 0; j < 8; ++j) {
-      x[j] = e0 + j < m ? c[e0 + j] : 0;
-      sum += x[j];
-    }
-    const uint32_t incl = wave_incl_add(sum, lane);
-    if (lane == 63) wt[wv] = incl;
-    __syncthreads();
-    uint32_t pre = carry, tot = 0;
-    for (uint32_t k = 0; k < 4; ++k) {
-      if (k < wv) pre += wt[k];
-      tot += wt[k];
-    }
-    uint32_t ex = pre + incl - sum;
-    for (uint32_t j = 0; j < 8; ++j)
-      if (e0 + j < m) {
-        c[e0 + j] = ex;
-        ex += x[j];
-      }
-    carry += tot;
-    __syncthreads();
-  }
-}
-
-// ... and the scatter, which keeps the input order among equal digits: rounds
-// in tile order, waves in order within a round, lanes ranked by ballot.
-__global__ __launch_bounds__(256) void upd_scatter_kernel(const uint32_t *key_in, const uint32_t *idx_in,
-                                                          uint32_t *key_out, uint32_t *idx_out, uint32_t n,
-                                                          uint32_t shift, const uint32_t *counts, uint32_t tiles) {
-  __shared__ uint32_t base[256];
-  __shared__ uint32_t wc[4][256];
-  const uint32_t tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  base[tid] = counts[(size_t)tid * tiles + blockIdx.x];
-  for (uint32_t k = 0; k < 4; ++k) wc[k][tid] = 0;
-  __syncthreads();
-  const uint64_t tile0 = (uint64_t)blockIdx.x * kSortTile;
-  for (uint32_t k = 0; k < kSortItems; ++k) {
-    const uint64_t e = tile0 + k * 256 + tid;
-    const bool valid = e < n;
-    const uint32_t kv = valid ? key_in[e] : 0;
-    const uint32_t d = (kv >> shift) & 255u;
-    unsigned long long m = __ballot(valid);
-    for (uint32_t bit = 0; bit < 8; ++bit) {
-      const bool on = (d >> bit) & 1u;
-      const unsigned long long b = __ballot(on);
-      m &= on ? b : ~b;
-    }
-    const uint32_t rank = __popcll(m & ((1ull << lane) - 1));
-    if (valid && rank == 0) wc[wv][d] = __popcll(m);
-    __syncthreads();
-    if (valid) {
-      uint32_t pos = base[d] + rank;
-      for (uint32_t q = 0; q < wv; ++q) pos += wc[q][d];
-      key_out[pos] = kv;
-      idx_out[pos] = idx_in[e];
-    }
-    __syncthreads();
-    base[tid] += wc[0][tid] + wc[1][tid] + wc[2][tid] + wc[3][tid];
-    for (uint32_t q = 0; q < 4; ++q) wc[q][tid] = 0;
-    __syncthreads();
-  }
 }
 
 // Segmented max: f = a segment head lies in the range, v = the maximum since
@@ -356,7 +249,7 @@ __global__ __launch_bounds__(256) void upd_scan_kernel(UpdArgs a) {
       } else {
         if (key[j] < a.nsa) {
           const espgpu_desc d = a.desc[a.order[p]];
-          const uint32_t seq = be32(*reinterpret_cast<const uint32_t *>(a.arena + (size_t)d.off4 * 4 + 4));
+          const uint32_t seq = bswap32(*reinterpret_cast<const uint32_t *>(a.arena + (size_t)d.off4 * 4 + 4));
           s[j] = (a.rp[key[j]].flags & ESPGPU_REPLAY_ESN) ? ((uint64_t)d.esn_hi << 32) | seq : seq;
         }
         a.w.sseq[p] = s[j];
@@ -424,7 +317,7 @@ __global__ __launch_bounds__(256) void upd_decide_kernel(UpdArgs a) {
   } else if (s > m) {
     ok = true;
   } else if (m - s < window) {
-    const uint32_t word = a.bitmap[r.bitmap_off + (uint32_t)((s >> 5) & (r.bitmap_size - 1))];
+    const uint32_t word = a.bitmap[replay_word(r, s)];
     const bool stale = (s >> 5) > (r.last >> 5);      // zeroed by an advance before this record
     ok = (stale || !((word >> (s & 31)) & 1u)) && hash_first(a, key, s, p);
   } else {
@@ -458,208 +351,31 @@ __global__ __launch_bounds__(256) void upd_set_kernel(UpdArgs a) {
   const espgpu_replay r = a.rp[key];
   const uint64_t s = a.w.sseq[p];
   if ((s >> 5) + r.bitmap_size > (a.w.sa_top[key] >> 5))
-    atomicOr(&a.bitmap[r.bitmap_off + (uint32_t)((s >> 5) & (r.bitmap_size - 1))], 1u << (s & 31));
+    atomicOr(&a.bitmap[replay_word(r, s)], 1u << (s & 31));
 }
-
-uint32_t upd_nsa(uint32_t nrp) { return nrp < 65536u ? nrp : 65536u; }
 
 size_t upd_carve(uint8_t *base, uint32_t n, uint32_t nrp, UpdWs *w) {
-  UpdWs t{};
-  t.hcap = hash_cap(n);
-  t.sort_tiles = (uint32_t)(((uint64_t)n + kSortTile - 1) / kSortTile);
-  t.scan_blocks = (uint32_t)(((uint64_t)n + kReplayScanBlock - 1) / kReplayScanBlock);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    uint8_t *p = base + off;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
-  t.sseq = (uint64_t *)take((size_t)n * 8);
-  t.top = (uint64_t *)take((size_t)n * 8);
-  t.agg_v = (uint64_t *)take((size_t)t.scan_blocks * 8);
-  t.car_v = (uint64_t *)take((size_t)t.scan_blocks * 8);
-  t.sa_top = (uint64_t *)take((size_t)upd_nsa(nrp) * 8);
-  for (int k = 0; k < 2; ++k) {
-    t.key[k] = (uint32_t *)take((size_t)n * 4);
-    t.idx[k] = (uint32_t *)take((size_t)n * 4);
-  }
-  t.hash = (uint32_t *)take((size_t)t.hcap * 4);
-  t.counts = (uint32_t *)take((size_t)t.sort_tiles * 256 * 4);
-  t.agg_f = (uint32_t *)take((size_t)t.scan_blocks * 4);
-  t.car_f = (uint32_t *)take((size_t)t.scan_blocks * 4);
-  if (w) *w = t;
-  return off;
-}
-
-// The stable grouping of n (key, index) pairs in key[0] / idx[0] by key: keys
-// are 0 .. nsa, so as many 8-bit passes as nsa has digits.  Returns which of
-// the two buffer pairs holds the result.
-int group_by_key(uint32_t *const key[2], uint32_t *const idx[2], uint32_t *counts, uint32_t tiles, uint32_t n,
-                 uint32_t nsa, hipStream_t st) {
-  const dim3 blk(256);
-  int cur = 0;
-  for (uint32_t shift = 0; (nsa >> shift) != 0; shift += 8) {
-    hipLaunchKernelGGL(upd_hist_kernel, dim3(tiles), blk, 0, st, key[cur], n, shift, counts, tiles);
-    hipLaunchKernelGGL(upd_scan_counts_kernel, dim3(1), blk, 0, st, counts, (uint64_t)tiles * 256);
-    hipLaunchKernelGGL(upd_scatter_kernel, dim3(tiles), blk, 0, st, key[cur], idx[cur], key[cur ^ 1],
-                       idx[cur ^ 1], n, shift, counts, tiles);
-    cur ^= 1;
-  }
-  return cur;
-}
-
-// ---- outbound framing ------------------------------------------------------------
-// espgpu_esp_frame_batch (include/espgpu.h).  esp_output hands
-// out an SA's sequence numbers and counter IVs one packet after another under
-// the SA lock; here a record's number is its SA's counter plus its rank among
-// that SA's taking-part records, and the rank is the record's position in
-// the batch grouped by SA (the stable sort above keeps arrival order) minus
-// the position of its SA's first record.  With room = esp_out_room(count0),
-// the records of rank < room are accepted and get count0 + rank + 1 and
-// cntr0 + rank; the SA ends at count0 + m, cntr0 + m, m = min(k, room).
-// Five steps: validate, group, segment heads, frame (reads the counters),
-// commit (writes them): every read of count / cntr precedes every write.
-struct FrmWs {
-  uint32_t *key[2], *idx[2];   // [n] sort buffers: SA (or nsa: takes no part), record index
-  uint32_t *counts;            // [256][sort tiles]
-  uint32_t *start;             // [nsa] grouped position of the SA's first record (SAs in the batch only)
-  uint32_t sort_tiles;
-};
-
-struct FrmArgs {
-  uint8_t *arena;
-  espgpu_desc *desc;
-  const uint32_t *frame;
-  espgpu_outsa *out;
-  const DevSA *sas;
-  uint8_t *fstatus;
-  const uint32_t *skey, *order;   // the sorted buffers
-  uint32_t n, nout, nsa, nsas;    // nsa = min(nout, 65536): the key of a record that takes no part
-  FrmWs w;
-};
-
-__device__ __forceinline__ bool frm_shape(const FrmArgs &a, uint32_t sa, uint32_t oflags, espgpu_eshape *s) {
-  const DevSA &d = a.sas[sa];
-  return esp_shape_of(d.mode, d.calg, d.mlen, oflags, s);
-}
-
-// Which records take part, and under which SA; the others are refused here.
-__global__ __launch_bounds__(256) void frm_prep_kernel(FrmArgs a) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.n) return;
-  const espgpu_desc d = a.desc[i];
-  const uint32_t rlen = a.frame[i] & 0xffffu;
-  uint32_t k = a.nsa;
-  if (d.sa < a.nout && d.sa < a.nsas) {
-    espgpu_eshape s;
-    if (frm_shape(a, d.sa, a.out[d.sa].flags, &s) &&
-        8 + s.ivlen + rlen + esp_padding(rlen, s.blks) + s.alen == (uint32_t)d.len)
-      k = d.sa;
-  }
-  a.w.key[0][i] = k;
-  a.w.idx[0][i] = i;
-  a.fstatus[i] = k == a.nsa ? ESPGPU_EINVAL : 0;
-  if (k == a.nsa) a.desc[i].len = 0;
-}
-
-__global__ __launch_bounds__(256) void frm_heads_kernel(FrmArgs a) {
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= a.n) return;
-  const uint32_t key = a.skey[p];
-  if (key < a.nsa && (p == 0 || a.skey[p - 1] != key)) a.w.start[key] = p;
-}
-
-// One lane per grouped position: the record's number and IV from its rank,
-// then the bytes esp_output writes.
-__global__ __launch_bounds__(256) void frm_frame_kernel(FrmArgs a) {
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= a.n) return;
-  const uint32_t key = a.skey[p];
-  if (key >= a.nsa) return;
-  const uint32_t i = a.order[p], rank = p - a.w.start[key];
-  const espgpu_outsa o = a.out[key];
-  if (rank >= esp_out_room(o.count, o.flags)) {       // the number space ended inside this batch
-    a.fstatus[i] = ESPGPU_EINVAL;
-    a.desc[i].len = 0;
-    return;
-  }
-  espgpu_eshape s;
-  if (!frm_shape(a, key, o.flags, &s)) return;        // (frm_prep_kernel accepted it)
-  const uint64_t count = o.count + rank + 1;
-  const uint32_t f = a.frame[i];
-  esp_frame_write(a.arena + (size_t)a.desc[i].off4 * 4, s, o.flags, o.spi, count, o.cntr + rank, f & 0xffffu,
-                  (uint8_t)(f >> 16));
-  a.desc[i].esn_hi = (o.flags & ESPGPU_OUT_ESN) ? (uint32_t)(count >> 32) : 0u;
-  if (s.ivlen == 8) a.desc[i].salt = o.salt;
-}
-
-// At the last grouped position of each SA: move its counters past what the
-// framing kernel gave out.
-__global__ __launch_bounds__(256) void frm_commit_kernel(FrmArgs a) {
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= a.n) return;
-  const uint32_t key = a.skey[p];
-  if (key >= a.nsa || (p + 1 < a.n && a.skey[p + 1] == key)) return;
-  const espgpu_outsa o = a.out[key];
-  const uint64_t k = (uint64_t)(p - a.w.start[key]) + 1, room = esp_out_room(o.count, o.flags);
-  const uint64_t m = k < room ? k : room;
-  espgpu_eshape s;
-  if (m == 0 || !frm_shape(a, key, o.flags, &s)) return;
-  a.out[key].count = o.count + m;
-  if (s.ivlen == 8) a.out[key].cntr = o.cntr + m;
-}
-
-size_t frm_carve(uint8_t *base, uint32_t n, uint32_t nout, FrmWs *w) {
-  FrmWs t{};
-  t.sort_tiles = (uint32_t)(((uint64_t)n + kSortTile - 1) / kSortTile);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    uint8_t *p = base + off;
-    off += (bytes + 255) & ~(size_t)255;
-    return p;
-  };
-  for (int k = 0; k < 2; ++k) {
-    t.key[k] = (uint32_t *)take((size_t)n * 4);
-    t.idx[k] = (uint32_t *)take((size_t)n * 4);
-  }
-  t.counts = (uint32_t *)take((size_t)t.sort_tiles * 256 * 4);
-  t.start = (uint32_t *)take((size_t)upd_nsa(nout) * 4);
-  if (w) *w = t;
-  return off;
+  WsCarver c{base};
+  w->hcap = hash_cap(n);
+  w->scan_blocks = (uint32_t)(((uint64_t)n + kReplayScanBlock - 1) / kReplayScanBlock);
+  w->sseq = c.take<uint64_t>(n);
+  w->top = c.take<uint64_t>(n);
+  w->agg_v = c.take<uint64_t>(w->scan_blocks);
+  w->car_v = c.take<uint64_t>(w->scan_blocks);
+  w->sa_top = c.take<uint64_t>(group_no_key(nrp));
+  group_carve(c, n, &w->g);
+  w->hash = c.take<uint32_t>(w->hcap);
+  w->agg_f = c.take<uint32_t>(w->scan_blocks);
+  w->car_f = c.take<uint32_t>(w->scan_blocks);
+  return c.off;
 }
 
 }  // namespace
 
-size_t esp_frame_workspace_bytes(uint32_t n, uint32_t nout) { return frm_carve(nullptr, n, nout, nullptr); }
-
-int launch_esp_frame(uint8_t *arena, espgpu_desc *desc, const uint32_t *frame, uint32_t n, espgpu_outsa *out,
-                     uint32_t nout, const DevSA *sas, uint32_t nsas, uint8_t *fstatus, void *ws, void *stream) {
-  if (n == 0) return 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 blk(256), grid_n((n + 255) / 256);
-  FrmArgs a{};
-  a.arena = arena;
-  a.desc = desc;
-  a.frame = frame;
-  a.out = out;
-  a.sas = sas;
-  a.fstatus = fstatus;
-  a.n = n;
-  a.nout = nout;
-  a.nsa = upd_nsa(nout);
-  a.nsas = nsas;
-  frm_carve(static_cast<uint8_t *>(ws), n, nout, &a.w);
-  hipLaunchKernelGGL(frm_prep_kernel, grid_n, blk, 0, st, a);
-  const int cur = group_by_key(a.w.key, a.w.idx, a.w.counts, a.w.sort_tiles, n, a.nsa, st);
-  a.skey = a.w.key[cur];
-  a.order = a.w.idx[cur];
-  hipLaunchKernelGGL(frm_heads_kernel, grid_n, blk, 0, st, a);
-  hipLaunchKernelGGL(frm_frame_kernel, grid_n, blk, 0, st, a);
-  hipLaunchKernelGGL(frm_commit_kernel, grid_n, blk, 0, st, a);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+size_t replay_update_workspace_bytes(uint32_t n, uint32_t nrp) {
+  UpdWs w;
+  return upd_carve(nullptr, n, nrp, &w);
 }
-
-size_t replay_update_workspace_bytes(uint32_t n, uint32_t nrp) { return upd_carve(nullptr, n, nrp, nullptr); }
 
 int launch_replay_update(const uint8_t *arena, const espgpu_desc *desc, uint32_t n, const uint8_t *status,
                          espgpu_replay *rp, uint32_t nrp, uint32_t *bitmap, uint8_t *ustatus, void *ws,
@@ -677,15 +393,15 @@ int launch_replay_update(const uint8_t *arena, const espgpu_desc *desc, uint32_t
   a.ustatus = ustatus;
   a.n = n;
   a.nrp = nrp;
-  a.nsa = upd_nsa(nrp);
+  a.nsa = group_no_key(nrp);
   upd_carve(static_cast<uint8_t *>(ws), n, nrp, &a.w);
   if (hipMemsetAsync(a.w.hash, 0xff, (size_t)a.w.hcap * 4, st) != hipSuccess ||
       hipMemsetAsync(a.w.sa_top, 0, (size_t)a.nsa * 8, st) != hipSuccess)
     return -1;
   hipLaunchKernelGGL(upd_prep_kernel, grid_n, blk, 0, st, a);
-  const int cur = group_by_key(a.w.key, a.w.idx, a.w.counts, a.w.sort_tiles, n, a.nsa, st);
-  a.skey = a.w.key[cur];
-  a.order = a.w.idx[cur];
+  const int cur = group_by_key(a.w.g, n, a.nsa, st);
+  a.skey = a.w.g.key[cur];
+  a.order = a.w.g.idx[cur];
   hipLaunchKernelGGL(upd_scan_kernel<false>, dim3(a.w.scan_blocks), blk, 0, st, a);
   hipLaunchKernelGGL(upd_scan_carry_kernel, dim3(1), blk, 0, st, a.w);
   hipLaunchKernelGGL(upd_scan_kernel<true>, dim3(a.w.scan_blocks), blk, 0, st, a);

@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "dev_prims.h"
 #include "espgpu_internal.h"
 #include "sha512_consts.h"
 
@@ -33,29 +34,6 @@ __device__ __forceinline__ uint32_t eopts() {
 #else
 __device__ __forceinline__ constexpr uint32_t eopts() { return 0; }
 #endif
-
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
-__device__ __forceinline__ uint32_t perm(uint32_t hi, uint32_t lo, uint32_t sel) {
-  return __builtin_amdgcn_perm(hi, lo, sel);
-}
-__device__ __forceinline__ uint32_t ror16(uint32_t x) { return __builtin_amdgcn_alignbit(x, x, 16); }
-__device__ __forceinline__ uint32_t rotl(uint32_t x, int n) { return __builtin_amdgcn_alignbit(x, x, 32 - n); }
-__device__ __forceinline__ uint32_t rotr(uint32_t x, int n) { return __builtin_amdgcn_alignbit(x, x, n); }
-__device__ __forceinline__ uint32_t bswap32(uint32_t x) { return perm(x, x, 0x00010203u); }
-
-// single 16- / 8-byte vector accesses at 4-byte alignment (see esp_gcm.hip)
-typedef uint32_t V4a __attribute__((ext_vector_type(4), aligned(4)));
-typedef uint32_t V2a __attribute__((ext_vector_type(2), aligned(4)));
-__device__ __forceinline__ uint4 ld16(const uint8_t *p) {
-  const V4a v = *reinterpret_cast<const V4a *>(p);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-__device__ __forceinline__ void st16(uint8_t *p, uint4 v) {
-  V4a u = {v.x, v.y, v.z, v.w};
-  *reinterpret_cast<V4a *>(p) = u;
-}
 
 // ---- SHA-1 compression (sha1_step, freebsd/crypto/sha1.c:94-176) ----------
 __device__ __forceinline__ void sha1_compress(uint32_t h[5], uint32_t w[16]) {

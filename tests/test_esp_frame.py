@@ -169,7 +169,7 @@ def test_shape_helper_refuses_ah_and_unserved_sessions():
 
 
 def _closed_form(desc, part, outsa, ctr_iv):
-    """The kernels' arithmetic (replay.hip): a stable sort by
+    """The kernels' arithmetic (frame.hip): a stable sort by
     SA, rank = grouped position - segment start, the first m = min(k, room)
     ranks accepted with count0 + rank + 1 and cntr0 + rank.  Returns (accepted,
     count, cntr per record; final count, cntr per SA)."""

@@ -1,4 +1,4 @@
-"""espgpu_esp_frame_batch (replay.hip): esp_output's framing for a
+"""espgpu_esp_frame_batch (frame.hip): esp_output's framing for a
 device-resident batch.  Every test compares the device batch with the host
 rule espgpu_esp_frame (pinned against esp.py's restatement of esp_output in
 test_esp_frame.py) applied in index order: the whole arena with random guard
@@ -12,7 +12,7 @@ from ah_helpers import AhSA
 from frame_helpers import EINVAL, host_frame_batch, layout, record_len, sa_kinds
 from helpers import EtaSA, GcmSA
 
-SORT_TILE = 2048           # records per workgroup of a radix pass (replay.hip kSortTile)
+SORT_TILE = 2048           # records per workgroup of a radix pass (sa_group.h kSortTile)
 NSES = 1100                # sessions of the module's driver
 DIGEST_SID, FREED_SID = 38, 39
 M64 = 2**64 - 1
@@ -93,9 +93,9 @@ def _frame_words(rng, rlen):
             (rng.integers(0, 256, len(rlen)) << 24)).astype(np.uint32)     # bits 24-31 are ignored
 
 
-def _run_and_compare(drv, shapes, arena, desc, frame, outsa, calls=None, stream=None):
+def _run_and_compare(drv, shapes, arena, desc, frame, outsa, calls=None, stream=None, between=None):
     """Upload, esp_frame (once, or per (start, count, nout) slice of `calls`
-    back to back without a sync), download, and compare everything with the
+    back to back without a sync, between(k) called after the k-th), download, and compare everything with the
     host rule applied to the same calls.  The outsa tensor has three guard
     entries past its end.  Returns the device (arena, desc, fstatus, outsa)."""
     torch = _torch()
@@ -111,9 +111,11 @@ def _run_and_compare(drv, shapes, arena, desc, frame, outsa, calls=None, stream=
     d_fst = torch.full((n + 8,), 0x77, dtype=torch.uint8, device="cuda")
     if stream is not None:
         stream.wait_stream(torch.cuda.current_stream())
-    for a, cnt, no in calls:
+    for k, (a, cnt, no) in enumerate(calls):
         esp_frame(drv, d_arena, d_desc[a * 16:], d_frame[a:], cnt, d_out[:no * OUTSA_DTYPE.itemsize], d_fst[a:],
                   stream=stream)
+        if between is not None:
+            between(k)
     if stream is not None:
         stream.synchronize()
     else:
@@ -140,7 +142,8 @@ def _run_and_compare(drv, shapes, arena, desc, frame, outsa, calls=None, stream=
     return g_arena, g_desc, g_fst[:n], g_out[:nout]
 
 
-def _batch(env, rng, sa, nout, rlen_max=96, outsa=None, wrong_len=0.0, calls=None, stream=None, rlen=None):
+def _batch(env, rng, sa, nout, rlen_max=96, outsa=None, wrong_len=0.0, calls=None, stream=None, rlen=None,
+           between=None):
     """Records of the sessions sa[i] with random payload lengths against a
     random (or the given) outsa table: frame on the device, compare."""
     sa = np.asarray(sa, dtype=np.int64)
@@ -151,7 +154,8 @@ def _batch(env, rng, sa, nout, rlen_max=96, outsa=None, wrong_len=0.0, calls=Non
     if wrong_len:
         bad = rng.random(len(sa)) < wrong_len
         desc["len"][bad] += rng.choice([-4, 4, 1, 16], int(bad.sum())).astype(np.uint16)
-    got = _run_and_compare(env.drv, shapes, arena, desc, _frame_words(rng, rlen), outsa, calls=calls, stream=stream)
+    got = _run_and_compare(env.drv, shapes, arena, desc, _frame_words(rng, rlen), outsa, calls=calls, stream=stream,
+                           between=between)
     return got, desc, outsa
 
 
@@ -269,6 +273,45 @@ def test_two_calls_without_a_sync_then_growth():
             (_, _, g_fst, g_out), _, outsa = _batch(e, rng, sa, 47, calls=calls, stream=stream, wrong_len=0.03)
             for s in range(20):
                 assert int(g_out["count"][s]) == int(outsa["count"][s]) + int(((g_fst == 0) & (sa == s)).sum())
+    finally:
+        e.drv.close()
+
+
+@pytest.mark.gpu
+def test_window_update_grows_the_workspace_a_framing_call_sized():
+    """Both stages carve one per-ctx workspace, sized in bytes by whoever asks.
+    On a fresh driver and one stream, with no sync in between: a framing call
+    of one record past a sort tile over 3 SAs allocates the (smaller) framing
+    layout, a window update of as many records over 257 windows (two radix
+    passes) has to grow it while the framing may still run, and a framing call
+    of 64 records is then carved from the larger buffer.  All three against
+    the host rules."""
+    torch = _torch()
+    from espgpu.batch import replay_update
+    from test_replay_update_gpu import _compare, _host_run, _records, _tables
+    rng = np.random.default_rng(9)
+    n, nwin = SORT_TILE + 1, 257
+    wins = [(1000 + 3 * k, 8, O.Replay(8).bitmap.size, O.REPLAY_ESN if k % 2 else 0, None) for k in range(nwin)]
+    tab, words = _tables(wins)
+    usa = rng.integers(0, nwin, n).astype(np.uint16)
+    useq = (1000 + 3 * usa.astype(np.int64) + rng.integers(-80, 40, n)).astype(np.uint32)
+    uarena, udesc = _records(usa, useq)
+    ustatus = np.where(rng.random(n) < 0.1, 80, 0).astype(np.uint8)
+    want = _host_run(tab, words, udesc, useq, ustatus)
+    assert (want[0] == 0).sum() > 200 and (want[0] != 0).sum() > 200
+    d_upd = [torch.from_numpy(x).cuda() for x in (uarena, udesc.view(np.uint8).copy(), ustatus, tab.view(np.uint8).copy(),
+                                                  words.view(np.int32).copy())]
+    d_ust = torch.full((n,), 0x77, dtype=torch.uint8, device="cuda")
+    e = Env(48)
+    try:
+        def update_after_the_first(k):
+            if k == 0:
+                replay_update(e.drv, d_upd[0], d_upd[1], n, d_upd[2], d_upd[3], d_upd[4], d_ust)
+        sa = rng.integers(0, 3, n + 64)
+        (_, _, g_fst, _), _, _ = _batch(e, rng, sa, 3, calls=[(0, n, 3), (n, 64, 3)], between=update_after_the_first)
+        assert (g_fst == 0).all()
+        _compare((d_ust.cpu().numpy(), d_upd[3].cpu().numpy().view(tab.dtype), d_upd[4].cpu().numpy().view(np.uint32)),
+                 want, n_guard_words=2 * (nwin + 1))
     finally:
         e.drv.close()
 

@@ -16,7 +16,7 @@ from test_replay_update64 import _seqs, _windows
 EACCES, EINVAL = 13, 22
 GUARD = 0xDEADBEEF
 SCAN_BLOCK = 1024          # grouped positions per workgroup of the max-scan (kReplayScanBlock)
-SORT_TILE = 2048           # records per workgroup of a radix pass (replay.hip kSortTile)
+SORT_TILE = 2048           # records per workgroup of a radix pass (sa_group.h kSortTile)
 DESC = np.dtype([("off4", "<u4"), ("len", "<u2"), ("sa", "<u2"), ("esn_hi", "<u4"), ("salt", "<u4")])
 
 
