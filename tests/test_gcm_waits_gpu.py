@@ -29,6 +29,7 @@ import pytest
 
 import oracle as O
 from helpers import GcmSA, build_records
+from sweep_helpers import _oracle, _payload_mask
 
 pytestmark = pytest.mark.gpu
 
@@ -66,33 +67,6 @@ def _sessions(drv, sas):
         assert rc == 0, drv.last_error()
         sids.append(sid)
     return sids
-
-
-def _oracle(sas, arena, descs, eh, keep, encrypt=False):
-    """The oracle over the records in `keep` (a bool per record), in a copy of
-    arena.  -> (arena after, one status per record; EINVAL where not kept)."""
-    out = arena.copy()
-    idx = np.nonzero(keep)[0]
-    st = np.full(len(descs), O.EINVAL, dtype=np.uint8)
-    _, s = O.batch([x.oracle for x in sas], out, descs["off4"][idx], descs["len"][idx], descs["sa"][idx],
-                   esn_hi=eh[idx], nthreads=8, encrypt=encrypt)
-    if encrypt:
-        # the oracle's encrypt reports no status: the records it refused are
-        # those it left untouched (an encrypted record gains at least its ICV)
-        for i in idx:
-            o, L = int(descs["off4"][i]) * 4, max(int(descs["len"][i]), 32)
-            st[i] = O.EINVAL if (out[o:o + L] == arena[o:o + L]).all() else 0
-    else:
-        st[idx] = s
-    return out, st
-
-
-def _payload_mask(descs, which, size, sas):
-    m = np.zeros(size, dtype=bool)
-    for i in np.nonzero(which)[0]:
-        o, L = int(descs["off4"][i]) * 4, int(descs["len"][i])
-        m[o + 16:o + L - sas[descs["sa"][i]].mlen] = True
-    return m
 
 
 def _check(drv, sas, sids, mode, src, descs, eh, foreign=None):
