@@ -3,21 +3,30 @@
 // that stage their own records (esp_gcm.hip, small single-session batches).
 //
 // Copies len bytes from src to dst (device or host-mapped addresses) with the
-// nt threads t = 0..nt-1 of the caller.  Both 16-byte aligned: dwordx4.
-// Otherwise destination-aligned dwords, each assembled from the two source
-// dwords it straddles (alignbyte), so every load and store is an aligned
-// dword and never touches a dword that holds no byte of the span; the
+// nt threads t = 0..nt-1 of the caller: any alignment of either side, any
+// length, any nt >= 1 (every loop strides over the threads; stage_in gives a
+// record as few as two).  Both 16-byte aligned: dwordx4, the <= 15 loose bytes
+// bytewise.  Otherwise destination-aligned dwords, each assembled from the
+// two source dwords it straddles (alignbyte), so every load and store is an
+// aligned dword and never touches a dword that holds no byte of the span; the
 // <= 3-byte head and tail go bytewise.  Records in mbufs start 2 mod 4.
+// tools/xfer_copy_selftest.cpp runs this header on the CPU over every
+// alignment pair, length and thread count.
 #pragma once
+#ifndef ESPGPU_HOST_SHIM   // tools/xfer_copy_selftest.cpp builds this header for the CPU
 #include <hip/hip_runtime.h>
+#endif
 #include <stdint.h>
 
 namespace espgpu {
 
 // Every load of a batch is issued before its stores (source and destination
 // never overlap), so a thread pays the read latency -- a PCIe round trip for
-// host memory -- once per kU elements, not once per element; the head and
-// tail bytes load with the first batch and store after the last.
+// host memory -- once per kU elements, not once per element; each thread's
+// first head and tail byte load with the first batch and store after the
+// last.  A thread has further loose bytes only where there are fewer threads
+// than loose bytes (nt < 15 of a 16-aligned pair, nt < 3 otherwise); those go
+// load by store at the end.
 template <int kU = 8>
 __device__ __forceinline__ void xfer_copy(uint64_t src_a, uint64_t dst_a, uint32_t len, uint32_t t,
                                           uint32_t nt) {
@@ -38,6 +47,7 @@ __device__ __forceinline__ void xfer_copy(uint64_t src_a, uint64_t dst_a, uint32
         if (i0 + u * nt < n16) d16[i0 + u * nt] = v[u];
     }
     if (tb < len) dst[tb] = tv;
+    for (uint32_t b = tb + nt; b < len; b += nt) dst[b] = src[b];
     return;
   }
   // head: bytes up to the first 4-byte-aligned destination address
@@ -71,6 +81,8 @@ __device__ __forceinline__ void xfer_copy(uint64_t src_a, uint64_t dst_a, uint32
   }
   if (hb) dst[t] = hv;
   if (tb) dst[tail0 + t] = tv;
+  for (uint32_t b = t + nt; b < head; b += nt) dst[b] = src[b];
+  for (uint32_t b = tail0 + t + nt; b < len; b += nt) dst[b] = src[b];
 }
 
 }  // namespace espgpu

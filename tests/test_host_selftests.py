@@ -63,6 +63,24 @@ def test_request_rule_selftest(tmp_path):
     assert r.stdout.startswith("OK")
 
 
+def test_staging_copy_selftest(tmp_path):
+    """The staging copy of the driver path (xfer_copy.h: the xfer kernel with
+    256 threads per piece, the GCM kernels' self-staging prologue with 64 down
+    to 2 threads per record), built for the CPU with v_alignbyte_b32 emulated
+    and its threads run one after the other, against memcpy: source residue
+    0..15 x destination residue 0..15, every length 0..160 and 4092..4100,
+    1 to 256 threads, both unroll factors -- the span copied, 32 guard bytes on
+    each side untouched, the source unchanged
+    (tools/xfer_copy_selftest.cpp)."""
+    exe = tmp_path / "xfer_copy_selftest"
+    csrc = os.path.join(ROOT, "f-stack_amd", "csrc")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-I", csrc, "-o", str(exe),
+                    os.path.join(ROOT, "tools", "xfer_copy_selftest.cpp")], check=True, timeout=300)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:]
+    assert r.stdout.startswith("OK 783360 combinations")
+
+
 def test_overflow_fifo_arena_selftest(tmp_path):
     """The host overflow's allocator (fifo_arena.h: a bip buffer of
     variable-length allocations, freed oldest first): 200 random alloc / pop

@@ -10,7 +10,8 @@ import subprocess
 import sys
 
 FIELDS = [("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("SGPRs", "sgpr"), ("VGPRs Spill", "vspill"),
-          ("SGPRs Spill", "sspill"), ("LDS Size [bytes/block]", "lds"), ("Occupancy [waves/SIMD]", "occ")]
+          ("SGPRs Spill", "sspill"), ("ScratchSize [bytes/lane]", "scratch"), ("LDS Size [bytes/block]", "lds"),
+          ("Occupancy [waves/SIMD]", "occ")]
 
 
 def parse(path):
@@ -47,8 +48,9 @@ def main():
             continue
         r = res[n]
         short = re.sub(r"espgpu::\(anonymous namespace\)::", "", d)
-        print("%-60s vgpr %3s sgpr %3s vspill %3s sspill %3s lds %6s occ %s" % (
-            short[:60], r.get("vgpr"), r.get("sgpr"), r.get("vspill"), r.get("sspill"), r.get("lds"), r.get("occ")))
+        print("%-60s vgpr %3s sgpr %3s vspill %3s sspill %3s scratch %4s lds %6s occ %s" % (
+            short[:60], r.get("vgpr"), r.get("sgpr"), r.get("vspill"), r.get("sspill"), r.get("scratch"), r.get("lds"),
+            r.get("occ")))
 
 
 if __name__ == "__main__":
