@@ -1,11 +1,12 @@
 // espgpu_batch.cpp — the kernel launches of the host runtime (espgpu_ctx.h):
 // run_batch, the device-resident batch entry points with their single-record
-// counterparts beside them (the rules are classify.h's, decap.h's, frame.h's
-// and replay.h's), and the host-to-host pipeline.
+// counterparts beside them (the rules are classify.h's, decap.h's, encap.h's,
+// frame.h's and replay.h's), and the host-to-host pipeline.
 #include "espgpu_ctx.h"
 
 #include "classify.h"      // (after the HIP runtime's vector types)
 #include "decap.h"
+#include "encap.h"
 #include "frame.h"
 #include "replay.h"
 
@@ -404,6 +405,61 @@ int espgpu_esp_decap_batch(espgpu_ctx *c, const uint8_t *d_arena, uint8_t *d_out
   return run_stage(c, n, 0, nullptr, "decap kernel launch failed", [&] {
     return launch_esp_decap(d_arena, d_out, d_pkt, d_desc, d_trailer, d_status, n, d_in, nin, c->d_sas,
                             c->cfg.max_sessions, d_ipkt, d_dstatus, stream);
+  });
+}
+
+// ---- outbound encapsulation ---------------------------------------------------
+// ipsec4/6_perform_request, ipsec_encap and the header work of esp_output and
+// ipsec_process_done for one packet.  The rule espgpu_esp_encap_batch applies
+// (encap.h).
+int espgpu_esp_encap(const espgpu_encsa *e, const espgpu_eshape *s, uint8_t *pkt, uint32_t len, uint32_t headroom,
+                     uint32_t tailroom, uint16_t ip_id, uint32_t *out_front, uint32_t *out_total,
+                     uint32_t *out_reclen, uint32_t *out_frame) {
+  for (uint32_t *r : {out_front, out_total, out_reclen, out_frame})
+    if (r) *r = 0;
+  if (!e || !s || !pkt || !out_front || !out_total || !out_reclen || !out_frame) return ESPGPU_EINVAL;
+  if ((s->ivlen != 0 && s->ivlen != 8 && s->ivlen != 16) || (s->blks != 4 && s->blks != 16) || s->alen > 0xffffu)
+    return ESPGPU_EINVAL;
+  EncapOut o;
+  const int st = esp_encap_rule(e, *s, pkt, len, headroom, tailroom, ip_id, &o);
+  if (st) return st;
+  *out_front = o.front;
+  *out_total = o.total;
+  *out_reclen = o.reclen;
+  *out_frame = o.frame;
+  return 0;
+}
+
+int espgpu_esp_sent(espgpu_encsa *e, uint8_t status, uint32_t len) {
+  if (!e) return ESPGPU_EINVAL;
+  if (status == 0) {
+    e->bytes += len;                                               // key.c:8429-8445
+    e->packets += 1;
+  }
+  return 0;
+}
+
+int espgpu_esp_encap_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_pkt *d_pkt, const uint16_t *d_sa, uint32_t n,
+                           const espgpu_encsa *d_enc, const espgpu_outsa *d_out, uint32_t nenc, uint32_t headroom,
+                           uint32_t tailroom, uint32_t id0, espgpu_desc *d_desc, uint32_t *d_frame,
+                           espgpu_pkt *d_opkt, uint8_t *d_estatus, void *stream) {
+  if (!c) return ESPGPU_EINVAL;
+  if (n && (!d_arena || !d_pkt || !d_sa || !d_desc || !d_frame || !d_opkt || !d_estatus ||
+            (nenc && (!d_enc || !d_out)) || ((uintptr_t)d_arena & 3)))
+    return ESPGPU_EINVAL;
+  // no workspace; of the ctx only the session table is read, as the crypto
+  // kernels read it
+  return run_stage(c, n, 0, nullptr, "encap kernel launch failed", [&] {
+    return launch_esp_encap(d_arena, d_pkt, d_sa, n, d_enc, d_out, nenc, c->d_sas, c->cfg.max_sessions, headroom,
+                            tailroom, id0, d_desc, d_frame, d_opkt, d_estatus, stream);
+  });
+}
+
+int espgpu_esp_sent_batch(espgpu_ctx *c, const espgpu_pkt *d_opkt, const espgpu_desc *d_desc, const uint8_t *d_status,
+                          uint32_t n, espgpu_encsa *d_enc, uint32_t nenc, void *stream) {
+  if (!c || (n && (!d_opkt || !d_desc || !d_status || (nenc && !d_enc)))) return ESPGPU_EINVAL;
+  return run_stage(c, n, 0, nullptr, "sent kernel launch failed", [&] {
+    return launch_esp_sent(d_opkt, d_desc, d_status, n, d_enc, nenc, stream);
   });
 }
 

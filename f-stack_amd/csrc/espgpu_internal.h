@@ -1,7 +1,7 @@
 // espgpu_internal.h — device-side data layouts shared by the host runtime
 // (espgpu*.cpp) and the HIP kernels (esp_gcm.hip, esp_cbc.hip, esp_ah.hip,
 // plan.hip, sa_group.hip, replay.hip, frame.hip, classify.hip, decap.hip,
-// xfer.hip).
+// encap.hip, xfer.hip).
 #pragma once
 #include <stdint.h>
 
@@ -260,6 +260,14 @@ int launch_esp_classify(const uint8_t *arena, const espgpu_pkt *pkt, uint32_t n,
 int launch_esp_decap(const uint8_t *arena, uint8_t *out, const espgpu_pkt *pkt, const espgpu_desc *desc,
                      const uint32_t *trailer, const uint8_t *status, uint32_t n, espgpu_insa *in, uint32_t nin,
                      const DevSA *sas, uint32_t nsas, espgpu_pkt *ipkt, uint8_t *dstatus, void *stream);
+// espgpu_esp_encap_batch and espgpu_esp_sent_batch (encap.hip; the rule is
+// encap.h's); nsas = the capacity of the DevSA table
+int launch_esp_encap(uint8_t *arena, const espgpu_pkt *pkt, const uint16_t *sa, uint32_t n, const espgpu_encsa *enc,
+                     const espgpu_outsa *out, uint32_t nenc, const DevSA *sas, uint32_t nsas, uint32_t headroom,
+                     uint32_t tailroom, uint32_t id0, espgpu_desc *desc, uint32_t *frame, espgpu_pkt *opkt,
+                     uint8_t *estatus, void *stream);
+int launch_esp_sent(const espgpu_pkt *opkt, const espgpu_desc *desc, const uint8_t *status, uint32_t n,
+                    espgpu_encsa *enc, uint32_t nenc, void *stream);
 int launch_xfer(const XferSpan *spans, uint32_t nspans, const uint8_t *status, void *stream);
 int launch_replay_merge(uint8_t *status, const uint8_t *rstatus, uint32_t n, void *stream);
 int launch_plan(const espgpu_desc *d_desc, uint32_t n, const DevSA *sas, uint32_t nsas, uint32_t cap_sas,

@@ -1,8 +1,8 @@
 // frame.h — the outbound framing rule (include/espgpu.h, the framing block):
 // one set of functions for espgpu_esp_frame on the host and the frm_* kernels
 // on the device (frame.hip): the shape of a session, how many numbers an SA may
-// still give out, and the bytes of one framed record.  decap.hip reads the
-// shape from it too.
+// still give out, and the bytes of one framed record.  decap.hip and encap.h
+// read the shape from it too.
 //
 // Plain C++ with no HIP header, as classify.h and decap.h: the host side also
 // builds with the host compiler alone.

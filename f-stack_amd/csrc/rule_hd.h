@@ -1,4 +1,4 @@
-// rule_hd.h — what the rule headers (classify.h, decap.h, frame.h, replay.h)
+// rule_hd.h — what the rule headers (classify.h, decap.h, encap.h, frame.h, replay.h)
 // share: the marker that makes one function serve the host entry point and the
 // kernel, and a packet dword in memory order.  Plain C++ with no HIP header.
 #pragma once

@@ -128,6 +128,21 @@ IN_TRANSPORT, IN_TUNNEL, IN_PAD_RAND, IN_AF6 = 0x1, 0x2, 0x4, 0x8
 ENODATA, EPFNOSUPPORT = 61, 96
 
 
+class EncSA(C.Structure):
+    """struct espgpu_encsa: one SA's outbound policy (ESPGPU_ENC_* flags, outer
+    ttl and addresses) and lifetime counters."""
+    _fields_ = [("bytes", C.c_uint64), ("packets", C.c_uint64), ("flags", C.c_uint32), ("ttl", C.c_uint8),
+                ("pad_", C.c_uint8 * 3), ("src", C.c_uint8 * 16), ("dst", C.c_uint8 * 16)]
+
+
+# the same as a numpy record, for batch.esp_encap's encsa tensor
+ENCSA_DTYPE = np.dtype([("bytes", "<u8"), ("packets", "<u8"), ("flags", "<u4"), ("ttl", "u1"), ("pad_", "u1", (3,)),
+                        ("src", "u1", (16,)), ("dst", "u1", (16,))])
+ENC_TUNNEL, ENC_AF6, ENC_DF_SET, ENC_DF_COPY = 0x01, 0x02, 0x04, 0x08
+ENC_ECN_ALLOWED, ENC_ECN_NOCARE, ENC_RFC6864 = 0x10, 0x20, 0x40
+EMSGSIZE, EAFNOSUPPORT, ENOBUFS = 90, 97, 105
+
+
 class Config(C.Structure):
     _fields_ = [("device", C.c_int), ("max_sessions", C.c_uint32),
                 ("batch_records", C.c_uint32), ("batch_bytes", C.c_uint32),
@@ -205,6 +220,14 @@ def lib():
             L.espgpu_esp_decap.argtypes = [C.POINTER(InSA), C.POINTER(EShape), vp, C.c_uint32, C.c_uint32,
                                            C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
             L.espgpu_esp_decap_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
+        if hasattr(L, "espgpu_esp_encap_batch"):        # (absent from older builds used in A/B runs)
+            u32p = C.POINTER(C.c_uint32)
+            L.espgpu_esp_encap.argtypes = [C.POINTER(EncSA), C.POINTER(EShape), vp, C.c_uint32, C.c_uint32,
+                                           C.c_uint32, C.c_uint16, u32p, u32p, u32p, u32p]
+            L.espgpu_esp_sent.argtypes = [C.POINTER(EncSA), C.c_uint8, C.c_uint32]
+            L.espgpu_esp_encap_batch.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32,
+                                                 C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
+            L.espgpu_esp_sent_batch.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp]
         L.espgpu_last_kernel_ms.argtypes = [vp]
         L.espgpu_last_kernel_ms.restype = C.c_float
         L.espgpu_set_tuning.argtypes = [vp, C.c_char_p, C.c_int]

@@ -210,6 +210,56 @@ def esp_decap(driver, arena, out, pkt, desc, trailer, status, n, insa, ipkt, dst
         raise RuntimeError("espgpu_esp_decap_batch: %s (%d)" % (driver.last_error(), rc))
 
 
+ENCSA_DTYPE = L.ENCSA_DTYPE
+assert ENCSA_DTYPE.itemsize == 56
+
+
+def esp_encap(driver, arena, pkt, sa, n, encsa, outsa, headroom, tailroom, id0, desc, frame, opkt, estatus,
+              stream=None):
+    """Outbound encapsulation, the step before esp_frame
+    (espgpu_esp_encap_batch): pkt is a uint8 CUDA tensor of PKT_DTYPE records
+    (cleartext IP packets in arena), sa an int16 CUDA tensor with the session
+    id the caller's SPD lookup chose for each, encsa a uint8 CUDA tensor of
+    ENCSA_DTYPE records and outsa esp_frame's OUTSA_DTYPE tensor, both indexed
+    by session id and equally long.  Every packet has headroom writable bytes
+    in front and tailroom behind, and the spans of one batch do not overlap.
+    Transport or tunnel is decided per packet; the header moves or the outer
+    header is built, with ip_id (id0 + i) & 0xffff.  desc, frame and opkt
+    receive what esp_frame takes and where the wire packet lies (PKT_DTYPE),
+    estatus 0 / EINVAL / ENOTSUP / EAFNOSUPPORT / EMSGSIZE / ENOBUFS for
+    replay_merge; a refused packet's descriptor has len 0 and sa 0xffff."""
+    for t in (arena, pkt, sa, encsa, outsa, desc, frame, opkt, estatus):
+        assert t.is_cuda and t.is_contiguous()
+    assert sa.element_size() == 2 and sa.numel() >= n and frame.element_size() == 4 and frame.numel() >= n
+    assert pkt.numel() * pkt.element_size() >= n * PKT_DTYPE.itemsize
+    assert opkt.numel() * opkt.element_size() >= n * PKT_DTYPE.itemsize
+    assert desc.numel() * desc.element_size() >= n * 16 and estatus.numel() >= n
+    nenc = encsa.numel() * encsa.element_size() // ENCSA_DTYPE.itemsize
+    assert outsa.numel() * outsa.element_size() // OUTSA_DTYPE.itemsize >= nenc
+    rc = driver.lib.espgpu_esp_encap_batch(
+        driver.ctx, arena.data_ptr(), pkt.data_ptr(), sa.data_ptr(), n, encsa.data_ptr(), outsa.data_ptr(), nenc,
+        headroom, tailroom, id0 & 0xffffffff, desc.data_ptr(), frame.data_ptr(), opkt.data_ptr(),
+        estatus.data_ptr(), _stream_ptr(stream))
+    if rc:
+        raise RuntimeError("espgpu_esp_encap_batch: %s (%d)" % (driver.last_error(), rc))
+
+
+def esp_sent(driver, opkt, desc, status, n, encsa, stream=None):
+    """The SAs' lifetime counters after the outbound merges
+    (espgpu_esp_sent_batch): every record with status 0 books its wire
+    packet's length and one packet into encsa[desc.sa]."""
+    for t in (opkt, desc, status, encsa):
+        assert t.is_cuda and t.is_contiguous()
+    assert opkt.numel() * opkt.element_size() >= n * PKT_DTYPE.itemsize
+    assert desc.numel() * desc.element_size() >= n * 16 and status.numel() >= n
+    nenc = encsa.numel() * encsa.element_size() // ENCSA_DTYPE.itemsize
+    rc = driver.lib.espgpu_esp_sent_batch(
+        driver.ctx, opkt.data_ptr(), desc.data_ptr(), status.data_ptr(), n, encsa.data_ptr(), nenc,
+        _stream_ptr(stream))
+    if rc:
+        raise RuntimeError("espgpu_esp_sent_batch: %s (%d)" % (driver.last_error(), rc))
+
+
 def replay_merge(driver, status, rstatus, n, stream=None):
     rc = driver.lib.espgpu_replay_merge(driver.ctx, status.data_ptr(), rstatus.data_ptr(), n,
                                         _stream_ptr(stream))

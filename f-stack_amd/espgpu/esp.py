@@ -4,6 +4,7 @@
   esp_input_crp()     esp_input          xform_esp.c:260-463
   esp_output_crp()    esp_output         xform_esp.c:673-961 (padding :710-716, :810-843)
   esp_trailer_ok()    esp_input_cb tail  xform_esp.c:597-636
+  ipsec_output_encap() ipsec4/6_perform_request, ipsec_encap  ipsec_output.c:221-242, :531-590, :882-992
 Records are IPv4 packets with the ESP header at `skip` (tunnel mode: skip = IP
 header length), in a bytearray (or an mbuf-like list of bytearrays).
 """
@@ -448,6 +449,143 @@ def esp_decap_host(insa, shape, buf, skip, rlen, trailer, at=0):
     rc = L.lib().espgpu_esp_decap(C.byref(insa), C.byref(shape), C.cast(raw, C.c_void_p), skip, rlen, trailer,
                                   C.byref(off), C.byref(ln))
     return rc, off.value, ln.value
+
+
+IP_DF, IP_MAXPACKET = 0x4000, 65535
+ECN_ALLOWED, ECN_FORBIDDEN, ECN_NOCARE = 1, 0, -1                    # netinet/ip_ecn.h
+
+
+def ip_ecn_ingress(mode, inner):
+    """The outer TOS / traffic class for an inner one (ip_ecn.c:97-122)."""
+    outer = inner
+    if mode == ECN_ALLOWED:
+        if inner & 3 == 3:                                           # CE inside: ECT(0) outside
+            outer &= ~1
+    elif mode == ECN_FORBIDDEN:
+        outer &= ~3
+    return outer & 0xff
+
+
+def ipsec_output_encap(tunnel, saf6, src, dst, ttl, dfbit, ecn, rfc6864, ivlen, blks, alen, packet, headroom,
+                       tailroom, ip_id):
+    """What the stack does with a cleartext packet between ip_output and
+    crypto_dispatch and after crypto_done, except the bytes esp_output_frame
+    covers: ipsec4_perform_request / ipsec6_perform_request
+    (ipsec_output.c:221-242, :531-590), ipsec_encap (:882-992) with
+    ip_ecn_ingress and ip_fillid's RFC 6864 rule (ip_id.c:252), esp_output's
+    size check, m_makespace, m_pad and protocol field (xform_esp.c:703-718,
+    :747, :772, :810, :839-843) and ipsec_process_done's length fields
+    (:722-745), with ip_output's checksum of a tunnel's outer IPv4 header
+    (ip_output.c:780-782) and a recomputed one for a transport header.  tunnel
+    is sp->req[idx]->saidx.mode == IPSEC_MODE_TUNNEL; saf6, src, dst describe
+    saidx (4 or 16 address bytes); ttl is V_ip_defttl / V_ip6_defhlim, dfbit
+    V_ip4_ipsec_dfbit (0, 1, 2), ecn V_ip4_ipsec_ecn / V_ip6_ipsec_ecn (-1, 0,
+    1), rfc6864 V_ip_rfc6864; ivlen, blks, alen are esp_output's; headroom and
+    tailroom stand for what m_makespace / ipsec_prepend and m_pad can get.
+    Returns (status, front, wire, nxt): the wire packet starts front bytes
+    before where the cleartext packet started, and `wire` holds it with None
+    for every byte the step leaves to framing and encryption (ESP header, IV,
+    padding, trailer, ICV); nxt is the byte m_copydata puts into the trailer.
+    (status, 0, None, 0) for a packet that is dropped.  A packet longer than
+    65535 bytes is EMSGSIZE for both families (the reference: ENXIO for IPv6,
+    :548-552, no check for IPv4), and link-local SA addresses are ENOTSUP:
+    their scope embedding (:975-981) needs the host's zone ids."""
+    m = bytes(packet)
+    src, dst = bytes(src), bytes(dst)
+    alen_a = 16 if saf6 else 4
+    hlen = 8 + ivlen
+    drop = lambda st: (st, 0, None, 0)                               # noqa: E731
+    if saf6:
+        if not any(src[:16]) or not any(dst[:16]):                   # :961-964
+            return drop(L.EINVAL)
+        if any(a[0] == 0xfe and a[1] & 0xc0 == 0x80 for a in (src, dst)):
+            return drop(L.ENOTSUP)
+    if len(m) < 20:                                                  # ip_output's own header
+        return drop(L.EINVAL)
+    v = m[0] >> 4
+    if v == 4:
+        skip = (m[0] & 0xf) << 2
+        if skip < 20 or skip > len(m):
+            return drop(L.EINVAL)
+        protoff, pdst = 9, m[16:20]
+    elif v == 6:
+        if len(m) < 40:
+            return drop(L.EINVAL)
+        skip, protoff, pdst = 40, 6, m[24:40]                        # :580-581
+    else:
+        return drop(L.EAFNOSUPPORT)                                  # :932-933
+    if len(m) > IP_MAXPACKET:
+        return drop(L.EMSGSIZE)
+    front = 0
+    encap = (tunnel or saf6 != (v == 6) or                           # :224-228, :543-547
+             (any(dst[:alen_a]) and dst[:alen_a] != pdst))
+    if encap:
+        if not saf6 and (not any(src[:4]) or not any(dst[:4])):      # :938-941
+            return drop(L.EINVAL)
+    # esp_output's lengths, before anything is written
+    oh = (40 if saf6 else 20) if encap else 0
+    eskip = oh if encap else skip
+    rlen = len(m) + oh - eskip                                       # m_pkthdr.len - skip, xform_esp.c:703
+    padding = ((blks - ((rlen + 2) % blks)) % blks) + 2              # :716
+    total = eskip + hlen + rlen + padding + alen
+    if total > IP_MAXPACKET:                                         # :747
+        return drop(L.EMSGSIZE)
+    if hlen + oh > headroom or padding + alen > tailroom:            # ipsec_prepend, m_makespace, m_pad
+        return drop(L.ENOBUFS)
+    m = bytearray(m)
+    if encap:
+        if v == 4:
+            setdf = dfbit if dfbit in (0, 1) else int(m[6] & 0x40 != 0)          # :910-917
+            itos, proto = m[1], IPPROTO_IPIP
+            m[2:4] = struct.pack(">H", len(m))                       # :230
+            m[10:12] = b"\0\0"                                       # :231
+            m[10:12] = struct.pack(">H", in_cksum(bytes(m[:skip])))  # :232
+        else:
+            m[4:6] = struct.pack(">H", len(m) - 40)                  # :533
+            itos, proto = (struct.unpack(">I", m[:4])[0] >> 20) & 0xff, IPPROTO_IPV6   # :925
+            setdf = 1 if dfbit else 0                                # :926
+        if not saf6:                                                 # :942-956
+            ip_off = IP_DF if setdf else 0
+            idv = 0 if rfc6864 and ip_off & IP_DF else ip_id & 0xffff            # ip_id.c:252
+            outer = bytearray(struct.pack(">BBHHHBBH4s4s", 0x45, ip_ecn_ingress(ecn, itos), len(m) + 20, idv,
+                                          ip_off, ttl, proto, 0, src[:4], dst[:4]))
+        else:                                                        # :965-984
+            outer = bytearray(struct.pack(">IHBB16s16s", 0x60000000 | ip_ecn_ingress(ecn, itos) << 20,
+                                          len(m), proto, ttl, src[:16], dst[:16]))
+        m = outer + m
+        front = oh
+        skip, protoff = (40, 6) if saf6 else (20, 9)                 # :568-582, :244-260
+    # esp_output: m_makespace(m, skip, hlen), m_pad(m, padding + alen)
+    wire = list(m[:skip]) + [None] * hlen + list(m[skip:]) + [None] * (padding + alen)
+    front += hlen
+    nxt = wire[protoff]                                              # :839
+    wire[protoff] = IPPROTO_ESP                                      # :842-843
+    assert len(wire) == total
+    if saf6:                                                         # ipsec_process_done, :742
+        wire[4:6] = list(struct.pack(">H", total - 40))
+    else:
+        wire[2:4] = list(struct.pack(">H", total))                   # :727
+        wire[10:12] = [0, 0]
+        wire[10:12] = list(struct.pack(">H", in_cksum(bytes(wire[:skip]))))      # ip_output.c:780-782
+    return 0, front, wire, nxt
+
+
+def esp_encap_host(encsa, shape, buf, at, length, headroom, tailroom, ip_id):
+    """espgpu_esp_encap, the engine's host rule, on a bytearray that holds the
+    cleartext packet at `at` and an L.EncSA: returns (status, front, total,
+    reclen, frame)."""
+    import ctypes as C
+    raw = (C.c_uint8 * (len(buf) - at)).from_buffer(buf, at) if len(buf) > at else None
+    res = [C.c_uint32(0xdddddddd) for _ in range(4)]
+    rc = L.lib().espgpu_esp_encap(C.byref(encsa), C.byref(shape), C.cast(raw, C.c_void_p) if raw else None, length,
+                                  headroom, tailroom, ip_id, *[C.byref(r) for r in res])
+    return (rc,) + tuple(r.value for r in res)
+
+
+def esp_sent_host(encsa, status, length):
+    """espgpu_esp_sent: key_sa_recordxfer for one wire packet on an L.EncSA."""
+    import ctypes as C
+    return L.lib().espgpu_esp_sent(C.byref(encsa), status, length)
 
 
 def trailer_word(plain_payload):

@@ -461,6 +461,8 @@ int  espgpu_replay_update_batch(espgpu_ctx *ctx, const uint8_t *d_arena,
  *                               trailer; fills desc.esn_hi and desc.salt
  *   2. espgpu_encrypt_batch     encrypt, ICV
  *   3. espgpu_replay_merge      with 1's result (d_status, d_fstatus, n).
+ * A caller that holds cleartext IP packets puts espgpu_esp_encap_batch in
+ * front and espgpu_esp_sent_batch behind (the encapsulation block below).
  * espgpu_esp_frame is the same rule on the host, one record per call. */
 #define ESPGPU_OUT_ESN       0x01    /* SADB_X_SAFLAGS_ESN: esn_hi = count >> 32 (:799)        */
 #define ESPGPU_OUT_CYCSEQ    0x02    /* SADB_X_EXT_CYCSEQ: the sequence number may cycle       */
@@ -708,6 +710,159 @@ int  espgpu_esp_decap_batch(espgpu_ctx *ctx, const uint8_t *d_arena, uint8_t *d_
                             const uint32_t *d_trailer, const uint8_t *d_status, uint32_t n,
                             struct espgpu_insa *d_in, uint32_t nin,
                             struct espgpu_pkt *d_ipkt, uint8_t *d_dstatus, void *stream);
+
+/* ---- outbound encapsulation (ipsec4_perform_request / ipsec6_perform_request,
+ *      ipsec_encap, esp_output's m_makespace / m_pad and protocol field, and
+ *      ipsec_process_done: freebsd/netipsec/ipsec_output.c:221-242, :531-590,
+ *      :720-770, :882-992, xform_esp.c:747, :772-780, :810-818, :839-843,
+ *      netinet/ip_ecn.c:97-122, ip_id.c:252, key.c:8429-8445) ----
+ * The steps around the framing block's sequence: from cleartext IP packets in
+ * the arena (what decapsulation produces, mirrored) to the ESP-shaped records
+ * espgpu_esp_frame_batch takes, and the SA's lifetime counters once a packet
+ * is on its way.  The outbound sequence on a device-resident batch, all on one
+ * stream:
+ *   1. espgpu_esp_encap_batch   transport or tunnel, outer header, header move,
+ *                               lengths, protocol field, checksum, size check;
+ *                               builds d_desc, d_frame and d_opkt
+ *   2. espgpu_esp_frame_batch   (the framing block above)
+ *   3. espgpu_encrypt_batch
+ *   4. espgpu_replay_merge      with 2's result (d_status, d_fstatus, n)
+ *   5. espgpu_replay_merge      with 1's (d_status, d_estatus, n)
+ *   6. espgpu_esp_sent_batch    key_sa_recordxfer for what went through
+ * d_opkt is then the list of wire packets, in the form
+ * espgpu_esp_classify_batch takes.  One SA's outbound policy and lifetime
+ * counters; the entry at index `sa` belongs to the session with that id.  Left
+ * to the caller or the host stack: the SPD lookup that picks the SA (d_sa),
+ * the hhooks / enc(4), random ip_id (ip_do_randomid needs a CSPRNG: the ids
+ * here are a counter's), link-local SA addresses (the scope embedding of
+ * ipsec_output.c:975-981), NAT-T, fragmentation of the result and
+ * ip_output of it. */
+#define ESPGPU_ENC_TUNNEL      0x01  /* sp->req[idx]->saidx.mode == IPSEC_MODE_TUNNEL          */
+#define ESPGPU_ENC_AF6         0x02  /* saidx.dst is AF_INET6; clear: AF_INET                  */
+#define ESPGPU_ENC_DF_SET      0x04  /* V_ip4_ipsec_dfbit 1: DF set in an outer IPv4 header    */
+#define ESPGPU_ENC_DF_COPY     0x08  /* V_ip4_ipsec_dfbit 2: copied from the inner header;
+                                        neither bit: clear; both: unusable                     */
+#define ESPGPU_ENC_ECN_ALLOWED 0x10  /* V_ip4_ipsec_ecn / V_ip6_ipsec_ecn 1 (ECN_ALLOWED)      */
+#define ESPGPU_ENC_ECN_NOCARE  0x20  /* -1 (ECN_NOCARE); neither bit: ECN_FORBIDDEN, the
+                                        default; both: unusable                                */
+#define ESPGPU_ENC_RFC6864     0x40  /* V_ip_rfc6864: ip_id 0 when DF is set (ip_id.c:252)     */
+#define ESPGPU_EMSGSIZE     90    /* the result would exceed IP_MAXPACKET (xform_esp.c:747)  */
+#define ESPGPU_EAFNOSUPPORT 97    /* the packet is neither IPv4 nor IPv6 (ipsec_output.c:933) */
+struct espgpu_encsa {             /* 56 B, indexed by session id, lives in device memory     */
+	uint64_t bytes;               /* lft_c_bytes                                             */
+	uint64_t packets;             /* lft_c_allocations                                       */
+	uint32_t flags;               /* ESPGPU_ENC_*                                            */
+	uint8_t  ttl;                 /* V_ip_defttl / V_ip6_defhlim: the outer header's value   */
+	uint8_t  pad_[3];
+	uint8_t  src[16];             /* saidx.src: 4 bytes + 12 zeros for AF_INET               */
+	uint8_t  dst[16];             /* saidx.dst                                               */
+};
+/* Host: encapsulate one cleartext packet of `len` bytes at `pkt` for SA `e`.
+ * `shape` is the session's (hlen = 8 + ivlen), `headroom` and `tailroom` the
+ * bytes before pkt and after pkt + len that the sequence may write, `ip_id`
+ * the value an outer IPv4 header gets.  Packets are in wire form (no embedded
+ * scope: ipsec_encap's in6_clearscope, ipsec_output.c:928-929, has nothing to
+ * do).  The checks in order; the first that fires decides, and a refused
+ * packet has nothing written and zeros in the four results:
+ *   1. flags with unknown bits, both DF bits or both ECN bits          EINVAL
+ *      an AF6 SA whose src or dst is unspecified (:961-964)            EINVAL
+ *      an AF6 SA whose src or dst is in fe80::/10 (the host's)         ENOTSUP
+ *   2. len < 20 (nothing is read)                                      EINVAL
+ *      version 4: ip_hl < 5 or ip_hl * 4 > len                         EINVAL
+ *        skip = ip_hl * 4, the protocol field is ip_p
+ *      version 6: len < 40                                             EINVAL
+ *        skip = 40 and the protocol field is ip6_nxt, extension headers or
+ *        not: ipsec6_perform_request passes sizeof(struct ip6_hdr) (:580)
+ *      any other version (:932-933)                                    EAFNOSUPPORT
+ *      len > 65535                                                     EMSGSIZE
+ *        (a deliberate difference: the reference answers ENXIO for an IPv6
+ *        inner packet here, :548-552, and has no such check for IPv4)
+ *   3. the packet is encapsulated (tunnel) if ESPGPU_ENC_TUNNEL is set, if
+ *      the SA's family differs from the packet's, or if the SA's dst is not
+ *      the unspecified address and differs from the packet's destination
+ *      (the proxy case; :224-228, :543-547); else transport.
+ *      tunnel, and an AF_INET SA's src or dst is zero (:938-941)       EINVAL
+ *   4. oh = 0 (transport), 20 or 40 (the outer header, by the SA's family);
+ *      rlen = len - skip (transport) or len (tunnel); padding as for
+ *      espgpu_esp_frame; total = (transport ? skip : oh) + hlen + rlen +
+ *      padding + alen.
+ *      total > 65535 (xform_esp.c:747)                                 EMSGSIZE
+ *      hlen + oh > headroom, or padding + alen > tailroom (where
+ *      m_makespace and m_pad would fail, :772-780, :810-818)           ENOBUFS
+ *   5. tunnel: first the inner header is fixed: IPv4 ip_len = len, ip_sum
+ *      zeroed and recomputed over ip_hl * 4 bytes (ipsec_output.c:230-232);
+ *      IPv6 ip6_plen = len - 40 (:533).  Then the outer header goes to pkt -
+ *      hlen - oh.  IPv4 (:946-956): version 4, ip_hl 5, TOS from
+ *      ip_ecn_ingress(mode, &tos, &itos) with itos the inner TOS or traffic
+ *      class, ip_len = total, ip_id = 0 with RFC6864 and DF set, else ip_id,
+ *      ip_off = DF by the policy (DF_COPY: the inner IPv4 DF bit; for an IPv6
+ *      inner packet DF is set iff either policy bit is, :926), ip_ttl = e->ttl,
+ *      ip_p = 50 (xform_esp.c:842-843), ip_src / ip_dst from the SA, ip_sum
+ *      over the finished 20 bytes (ip_output.c:780-782).  IPv6 (:969-984):
+ *      flow 0, version 6, the class from ip_ecn_ingress, ip6_plen = total - 40
+ *      (:742), ip6_nxt = 50, ip6_hlim = e->ttl, the SA's addresses.  The next
+ *      header of the frame word is 4 or 41 (xform_esp.c:839).
+ *   6. transport: the skip header bytes move from pkt to pkt - hlen, every
+ *      dword loaded before the first is stored (the ranges overlap whenever
+ *      hlen < skip).  IPv4: ip_len = total (ipsec_output.c:727), ip_p = 50
+ *      with the old value as the next header, ip_sum recomputed over skip
+ *      bytes.  IPv6: ip6_plen = total - 40, ip6_nxt = 50 likewise.  Options
+ *      and everything else in the header stay.
+ *   7. *out_front = hlen + oh: the wire packet is {pkt - *out_front,
+ *      *out_total}.  The ESP record is its last *out_reclen = hlen + rlen +
+ *      padding + alen bytes, the length espgpu_esp_frame takes: it starts
+ *      behind the outer header (at pkt - hlen) or behind the moved header (at
+ *      pkt - hlen + skip), 4-byte aligned with pkt.  *out_frame = rlen | next
+ *      header << 16.
+ * Only the header bytes named above are written: not the payload, the ESP
+ * header, the IV, the padding, the trailer or the ICV field, which are
+ * framing's and encryption's.  The counters are espgpu_esp_sent's.  Null
+ * pointers and an unusable shape are EINVAL. */
+int  espgpu_esp_encap(const struct espgpu_encsa *e, const struct espgpu_eshape *shape, uint8_t *pkt,
+                      uint32_t len, uint32_t headroom, uint32_t tailroom, uint16_t ip_id,
+                      uint32_t *out_front, uint32_t *out_total, uint32_t *out_reclen,
+                      uint32_t *out_frame);
+/* Host: key_sa_recordxfer of ipsec_process_done (ipsec_output.c:770) for one
+ * packet that went through with status `status`: 0 books `len` bytes (the wire
+ * packet's total) and one packet into *e, anything else nothing.  Returns 0,
+ * or EINVAL for a null e. */
+int  espgpu_esp_sent(struct espgpu_encsa *e, uint8_t status, uint32_t len);
+/* The same rule for n packets of a device-resident arena.  d_pkt[i] is the
+ * cleartext packet, d_sa[i] the SA the caller's SPD lookup chose for it,
+ * d_enc[nenc] and d_out[nenc] are indexed by the session id (of d_out only
+ * flags is read, for ESPGPU_OUT_CTRCOMPAT).  Packet i takes part if d_sa[i] <
+ * nenc and the ctx holds an ESP session with that id (as
+ * espgpu_esp_frame_batch: not a DIGEST session, not a free slot); its shape
+ * is that session's and its ip_id (uint16_t)(id0 + i): the caller adds n to
+ * its counter.  (ip_fillid draws from a per-CPU counter only for the packets
+ * that need one, ip_id.c:257; here ids stay distinct within a batch.)
+ * headroom and tailroom hold for every packet, and the caller guarantees that
+ * the spans [pkt - headroom, pkt + len + tailroom) of one batch lie in the
+ * arena and do not overlap.  An accepted packet gets d_desc[i] = {record off4,
+ * *out_reclen, sa, 0, 0}, d_frame[i] = *out_frame, d_opkt[i] = {wire off4,
+ * *out_total} and d_estatus[i] = 0.  A refused packet gets its status, one
+ * that takes no part EINVAL, and both d_desc[i] = {d_pkt[i].off4, 0, 0xffff,
+ * 0, 0} (classification's empty descriptor: framing refuses it, encryption
+ * passes over it) and d_opkt[i] = {d_pkt[i].off4, 0}.  d_arena is 4-byte
+ * aligned (EINVAL otherwise).  One lane per packet, asynchronous on the
+ * caller's stream, no workspace, no host round trip; n == 0 is a no-op that
+ * returns 0. */
+int  espgpu_esp_encap_batch(espgpu_ctx *ctx, uint8_t *d_arena, const struct espgpu_pkt *d_pkt,
+                            const uint16_t *d_sa, uint32_t n, const struct espgpu_encsa *d_enc,
+                            const struct espgpu_outsa *d_out, uint32_t nenc, uint32_t headroom,
+                            uint32_t tailroom, uint32_t id0, struct espgpu_desc *d_desc,
+                            uint32_t *d_frame, struct espgpu_pkt *d_opkt, uint8_t *d_estatus,
+                            void *stream);
+/* espgpu_esp_sent for a batch, after the merges: a record with d_status[i] ==
+ * 0 and d_desc[i].sa < nenc books d_opkt[i].len bytes and one packet into
+ * d_enc[sa].  A step of its own because a record that framing refuses
+ * (WRAPCHECK) never reaches ipsec_process_done in the reference either.  The
+ * sums are order-free: summed per wave, and per workgroup where one SA has all
+ * of it, before the 64-bit adds, as espgpu_esp_decap_batch's.  Asynchronous on
+ * the caller's stream, no workspace; n == 0 is a no-op that returns 0. */
+int  espgpu_esp_sent_batch(espgpu_ctx *ctx, const struct espgpu_pkt *d_opkt,
+                           const struct espgpu_desc *d_desc, const uint8_t *d_status, uint32_t n,
+                           struct espgpu_encsa *d_enc, uint32_t nenc, void *stream);
 
 /* Device time of the last timed batch's crypto kernels (ms, from HIP events
  * on the batch stream).  Process-path batches of <= 128 KiB (a burst on its
