@@ -6,6 +6,8 @@
 
 #include <stdint.h>
 
+#include "bounds_chk.h"
+
 namespace espgpu {
 
 namespace {
@@ -54,6 +56,73 @@ __device__ __forceinline__ void st_partial(uint8_t *p, uint4 v, int rem) {
     *reinterpret_cast<uint32_t *>(p) = v.x;
   if (rem > 8) *reinterpret_cast<uint32_t *>(p + 8) = v.z;
 }
+
+// The other global-memory accesses of esp_gcm.hip and esp_ah.hip, spelled once so that the bounds-checked build
+// (bounds_chk.h) can stand in front of every one of them: a 4-byte access at a
+// record pointer; element i of a per-record array, of the chunk list or of the
+// SA table (K: the CHK_* kind that names its bound), loaded, stored or
+// addressed; a descriptor as one 16-byte load.  Here each is the single
+// access it spells.  (esp_ld4w: dword k at a dword pointer formed from a
+// record pointer.)
+#ifndef ESPGPU_BOUNDS
+#define esp_ld4(p) (*reinterpret_cast<const uint32_t *>(p))
+#define esp_st4(p, v) (*reinterpret_cast<uint32_t *>(p) = (v))
+#define esp_ld4w(q, k) ((q)[k])
+#define esp_at_ld(K, a, i) ((a)[i])
+#define esp_at_st(K, a, i, v) ((a)[i] = (v))
+#define esp_at_ptr(K, a, i) ((a) + (i))
+#define esp_desc_ld16(a, i) (*reinterpret_cast<const uint4 *>((a) + (i)))
+#else
+#ifndef ESPGPU_CHK_TAG
+#define ESPGPU_CHK_TAG 0   // a file outside the checked three: its block is never set, nothing is checked
+#endif
+#define CHK_SITE ((uint32_t)(ESPGPU_CHK_TAG) << 16 | (uint32_t)__LINE__)
+__device__ __forceinline__ uint4 chk_ld16(const uint8_t *p, uint32_t site) {
+  return chk_range(p, 16, false, site) ? ld16(p) : make_uint4(0, 0, 0, 0);
+}
+__device__ __forceinline__ void chk_st16(uint8_t *p, uint4 v, uint32_t site) {
+  if (chk_range(p, 16, true, site)) st16(p, v);
+}
+__device__ __forceinline__ void chk_st8(uint8_t *p, uint32_t a, uint32_t b, uint32_t site) {
+  if (chk_range(p, 8, true, site)) st8(p, a, b);
+}
+__device__ __forceinline__ void chk_st_partial(uint8_t *p, uint4 v, int rem, uint32_t site) {
+  if (chk_range(p, rem >= 16 ? 16u : (uint32_t)rem, true, site)) st_partial(p, v, rem);
+}
+__device__ __forceinline__ uint32_t chk_ld4(const uint8_t *p, uint32_t site) {
+  return chk_range(p, 4, false, site) ? *reinterpret_cast<const uint32_t *>(p) : 0u;
+}
+__device__ __forceinline__ void chk_st4(uint8_t *p, uint32_t v, uint32_t site) {
+  if (chk_range(p, 4, true, site)) *reinterpret_cast<uint32_t *>(p) = v;
+}
+template <class T>
+__device__ __forceinline__ T chk_at_ld(uint32_t kind, const T *a, uint64_t i, uint32_t site) {
+  return chk_index(kind, i, site) ? a[i] : T{};
+}
+template <class T, class V>
+__device__ __forceinline__ void chk_at_st(uint32_t kind, T *a, uint64_t i, V v, uint32_t site) {
+  if (chk_index(kind, i, site)) a[i] = (T)v;
+}
+template <class T>
+__device__ __forceinline__ T *chk_at_ptr(uint32_t kind, T *a, uint64_t i, uint32_t site) {
+  return a + (chk_index(kind, i, site) ? i : 0);
+}
+template <class T>
+__device__ __forceinline__ uint4 chk_desc_ld16(const T *a, uint64_t i, uint32_t site) {
+  return chk_index(CHK_DESC, i, site) ? *reinterpret_cast<const uint4 *>(a + i) : make_uint4(0, 0, 0, 0);
+}
+#define ld16(p) chk_ld16((p), CHK_SITE)
+#define st16(p, v) chk_st16((p), (v), CHK_SITE)
+#define st8(p, a, b) chk_st8((p), (a), (b), CHK_SITE)
+#define st_partial(p, v, rem) chk_st_partial((p), (v), (rem), CHK_SITE)
+#define esp_ld4(p) chk_ld4((p), CHK_SITE)
+#define esp_st4(p, v) chk_st4((p), (v), CHK_SITE)
+#define esp_ld4w(q, k) chk_ld4(reinterpret_cast<const uint8_t *>(q) + 4 * (k), CHK_SITE)
+#define esp_at_ld(K, a, i) chk_at_ld((K), (a), (i), CHK_SITE)
+#define esp_at_st(K, a, i, v) chk_at_st((K), (a), (i), (v), CHK_SITE)
+#define esp_at_ptr(K, a, i) chk_at_ptr((K), (a), (i), CHK_SITE)
+#define esp_desc_ld16(a, i) chk_desc_ld16((a), (i), CHK_SITE)
+#endif
 
 __device__ __forceinline__ uint4 xor4(uint4 a, uint4 b) {
   return make_uint4(a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w);

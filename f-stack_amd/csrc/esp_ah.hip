@@ -29,6 +29,7 @@
 
 #include <algorithm>
 
+#define ESPGPU_CHK_TAG 3   // (bounds_chk.h site ids)
 #include "espgpu_internal.h"
 #include "sha_dev.h"
 
@@ -46,7 +47,7 @@ __device__ __forceinline__ uint32_t msg_word(const uint8_t *rec, uint32_t o, uin
                                              uint32_t s_hi, uint32_t s_lo, uint32_t hlo, uint32_t hhi) {
   uint32_t v = 0;
   if (o < L0) {                                   // (at most the dword holding byte L0 - 1)
-    v = bswap32(*reinterpret_cast<const uint32_t *>(rec + o));
+    v = bswap32(esp_ld4(rec + o));
     if (o == ob) v &= ~(0xffffffffu >> sh);       // (o == ob < L0: sh is 8, 16 or 24)
     if (o >= hlo && o < hhi) v = 0;
   }
@@ -260,20 +261,20 @@ __global__ __launch_bounds__(kDigWG) void digest_kernel(DigestParams p) {
       di = u * 64 + lane;
       have = di < p.n;
     } else {
-      const Chunk ch = p.chunks[u];
+      const Chunk ch = esp_at_ld(CHK_CHUNKS, p.chunks, u);
       have = (uint32_t)lane < ch.count;
-      if (have) di = p.order[ch.start + lane];
+      if (have) di = esp_at_ld(CHK_ORDER, p.order, ch.start + lane);
     }
     bool mine = false, valid = false, verify = false, esn = false, ok = false;
     uint32_t off = 0, len = 0, sa = 0, esnh = 0, icvo = 0, mlen = 0;
     int hq = 0;                                   // narrow: 1 SHA-1, 2 SHA2-256; wide: 1 SHA2-384, 2 SHA2-512
     if (have) {
-      const uint4 dv = *reinterpret_cast<const uint4 *>(p.desc + di);
+      const uint4 dv = esp_desc_ld16(p.desc, di);
       off = dv.x * 4;
       len = dv.y & 0xffffu;
       sa = dv.y >> 16;
       esnh = dv.z;
-      const DevSA *s = sa < p.nsas ? p.sas + sa : nullptr;
+      const DevSA *s = sa < p.nsas ? esp_at_ptr(CHK_SAS, p.sas, sa) : nullptr;
       if (s && s->mode == ESPGPU_CSP_MODE_DIGEST && wide_hash(s->aalg) == WIDE) {
         mine = true;
         mlen = s->mlen;
@@ -293,25 +294,25 @@ __global__ __launch_bounds__(kDigWG) void digest_kernel(DigestParams p) {
     if (WIDE) {
       if (__any(hq != 0)) {
         const bool act = hq != 0;
-        const DevSA *s = p.sas + (act ? sa : 0u);
+        const DevSA *s = esp_at_ptr(CHK_SAS, p.sas, act ? sa : 0u);
         uint32_t dg[16];
         digest_quad_wide(act, rec, len, esn, esnh, hlo, hhi, hq == 1, kp(s->ipad), kp(s->opad), dg);
         // (the block loop has ended for every lane: the ICV may be stored)
         if (act && verify) {
           uint32_t diff = 0;
           for (uint32_t k = 0; k < mlen / 4; ++k)
-            diff |= bswap32(dg[k]) ^ *reinterpret_cast<const uint32_t *>(rec + icvo + 4 * k);
+            diff |= bswap32(dg[k]) ^ esp_ld4(rec + icvo + 4 * k);
           ok = diff == 0;
         } else if (act) {
           for (uint32_t k = 0; k < mlen / 4; ++k)
-            *reinterpret_cast<uint32_t *>(p.icv_out + off + icvo + 4 * k) = bswap32(dg[k]);
+            esp_st4(p.icv_out + off + icvo + 4 * k, bswap32(dg[k]));
         }
       }
     } else {
       for (int hs = 1; hs <= 2; ++hs) {           // (not unrolled: two digest_quad bodies)
         if (!__any(hq == hs)) continue;           // wave-uniform
         const bool act = hq == hs;
-        const DevSA *s = p.sas + (act ? sa : 0u);
+        const DevSA *s = esp_at_ptr(CHK_SAS, p.sas, act ? sa : 0u);
         uint32_t dg[16];
         if (hs == 2)
           digest_quad<HS_SHA256>(act, rec, len, esn, esnh, hlo, hhi, kp(s->ipad), kp(s->opad), dg);
@@ -322,18 +323,18 @@ __global__ __launch_bounds__(kDigWG) void digest_kernel(DigestParams p) {
         if (act && verify) {
           uint32_t diff = 0;
           for (uint32_t k = 0; k < mlen / 4; ++k)
-            diff |= bswap32(dg[k]) ^ *reinterpret_cast<const uint32_t *>(rec + icvo + 4 * k);
+            diff |= bswap32(dg[k]) ^ esp_ld4(rec + icvo + 4 * k);
           ok = diff == 0;
         } else if (act) {
           for (uint32_t k = 0; k < mlen / 4; ++k)
-            *reinterpret_cast<uint32_t *>(p.icv_out + off + icvo + 4 * k) = bswap32(dg[k]);
+            esp_st4(p.icv_out + off + icvo + 4 * k, bswap32(dg[k]));
         }
       }
     }
     if (mine) {
       const bool good = valid && (ok || !verify);
-      p.status[di] = !valid ? ESPGPU_EINVAL : (good ? ESPGPU_OK : ESPGPU_EBADMSG);
-      if (p.trailer) p.trailer[di] = good ? ESPGPU_TR_VALID : 0u;
+      esp_at_st(CHK_STATUS, p.status, di, !valid ? ESPGPU_EINVAL : (good ? ESPGPU_OK : ESPGPU_EBADMSG));
+      if (p.trailer) esp_at_st(CHK_TRAILER, p.trailer, di, good ? ESPGPU_TR_VALID : 0u);
     }
   }
   // Every wave leaves the loop after drawing one ticket past the end, so once
@@ -357,6 +358,9 @@ int launch_digest(const DigestParams &p, int narrow, int wide, int grid, void *s
     const int units = (int)((p.n + 63) / 64), wpg = kDigWG / 64;
     return std::max(1, std::min(g, (units + wpg - 1) / wpg));
   };
+#ifdef ESPGPU_BOUNDS
+  ESPGPU_CHK_SET(p.chk, st);
+#endif
   if (narrow) hipLaunchKernelGGL((digest_kernel<false>), dim3(clamp(3 * grid)), dim3(kDigWG), 0, st, p);
   if (wide) hipLaunchKernelGGL((digest_kernel<true>), dim3(clamp(2 * grid)), dim3(kDigWG), 0, st, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;

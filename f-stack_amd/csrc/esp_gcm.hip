@@ -48,6 +48,7 @@
 
 #include <algorithm>
 
+#define ESPGPU_CHK_TAG 1   // (bounds_chk.h site ids)
 #include "dev_prims.h"
 #include "espgpu_internal.h"
 #include "xfer_copy.h"
@@ -600,7 +601,7 @@ __device__ __forceinline__ void do_group(const GcmParams &p, const uint8_t *lds,
   uint32_t len = 0, spi = 0, sn = 0, esnh = 0;
   uint32_t s0c = 0, s1c = 0, s2c = 0;
   if (have) {
-    const uint4 dv = *reinterpret_cast<const uint4 *>(p.desc + di);
+    const uint4 dv = esp_desc_ld16(p.desc, di);
     len = dv.y & 0xffffu;
     ct_len = (int)len - 16 - (int)mlen;                      // 8 hdr + 8 IV + ICV
     valid = ((dv.y >> 16) == sa) && ct_len > 0 && (len & 3) == 0 &&   // xform_esp.c:279-324
@@ -626,8 +627,8 @@ __device__ __forceinline__ void do_group(const GcmParams &p, const uint8_t *lds,
   GCM_PHASE(8, true);
   const bool want_trl = MODE != 1 && p.trailer != nullptr;
   if (Mw == 0) {
-    if (have && l == 0 && !valid) p.status[di] = ESPGPU_EINVAL;
-    if (have && l == 0 && want_trl) p.trailer[di] = 0;
+    if (have && l == 0 && !valid) esp_at_st(CHK_STATUS, p.status, di, ESPGPU_EINVAL);
+    if (have && l == 0 && want_trl) esp_at_st(CHK_TRAILER, p.trailer, di, 0);
     return;
   }
   const uint32_t rk3 = rk[3];
@@ -870,9 +871,9 @@ __device__ __forceinline__ void do_group(const GcmParams &p, const uint8_t *lds,
     if (mlen == 16) {
       tag = ld16(rec + len - mlen);
     } else {
-      tag.x = q[0];
-      tag.y = q[1];
-      if (mlen > 8) tag.z = q[2];
+      tag.x = esp_ld4w(q, 0);
+      tag.y = esp_ld4w(q, 1);
+      if (mlen > 8) tag.z = esp_ld4w(q, 2);
     }
   }
   // X = sum_l Y_l * H^(8-l)  (power index 7-l)
@@ -905,10 +906,10 @@ __device__ __forceinline__ void do_group(const GcmParams &p, const uint8_t *lds,
     // exactly one lane of the record holds it: OR over the 8 lanes
 #pragma unroll
     for (int o = 1; o < S; o <<= 1) trl |= __shfl_xor(trl, o);
-    if (have && l == 0) p.trailer[di] = (valid && ok) ? trl : 0u;
+    if (have && l == 0) esp_at_st(CHK_TRAILER, p.trailer, di, (valid && ok) ? trl : 0u);
   }
   if (have && l == 0)
-    p.status[di] = !valid ? ESPGPU_EINVAL : (ok ? ESPGPU_OK : ESPGPU_EBADMSG);
+    esp_at_st(CHK_STATUS, p.status, di, !valid ? ESPGPU_EINVAL : (ok ? ESPGPU_OK : ESPGPU_EBADMSG));
 }
 
 // ---- the burst design's two halves: a CTR pass and a GHASH / tag pass ----------
@@ -942,7 +943,7 @@ __device__ __forceinline__ void ctr_group(const GcmParams &p, const uint8_t *lds
   uint8_t *rec = p.arena;
   uint32_t s0c = 0, s1c = 0, s2c = 0;
   if (have) {
-    const uint4 dv = *reinterpret_cast<const uint4 *>(p.desc + di);
+    const uint4 dv = esp_desc_ld16(p.desc, di);
     const uint32_t len = dv.y & 0xffffu;
     ct_len = (int)len - 16 - (int)mlen;
     valid = ((dv.y >> 16) == sa) && ct_len > 0 && (len & 3) == 0;
@@ -977,8 +978,8 @@ __device__ __forceinline__ void ctr_group(const GcmParams &p, const uint8_t *lds
     const uint4 o = xor4(C, ks);
     st_partial(orec + 16 + 16 * i, o, rem);
     if (want_trl && i == nct - 1)
-      p.trailer[di] = esp_trailer_word(rem >= 16 ? o.w : (rem > 8 ? o.z : (rem > 4 ? o.y : o.x)),
-                                       (uint32_t)ct_len);
+      esp_at_st(CHK_TRAILER, p.trailer, di, esp_trailer_word(rem >= 16 ? o.w : (rem > 8 ? o.z : (rem > 4 ? o.y : o.x)),
+                                       (uint32_t)ct_len));
   };
   for (int k = 0; k < Kw; k += 2) {
     const int ia = l - 1 + S * k, ib = ia + S;
@@ -1020,7 +1021,7 @@ __device__ __forceinline__ void tag_group(const GcmParams &p, const uint8_t *lds
   uint8_t *rec = p.arena;
   uint32_t len = 0, spi = 0, sn = 0, esnh = 0;
   if (have) {
-    const uint4 dv = *reinterpret_cast<const uint4 *>(p.desc + di);
+    const uint4 dv = esp_desc_ld16(p.desc, di);
     len = dv.y & 0xffffu;
     ct_len = (int)len - 16 - (int)mlen;
     valid = ((dv.y >> 16) == sa) && ct_len > 0 && (len & 3) == 0;
@@ -1043,8 +1044,8 @@ __device__ __forceinline__ void tag_group(const GcmParams &p, const uint8_t *lds
   const bool want_trl = DIR == 0 && p.trailer != nullptr;
   if (Mw == 0) {
     if (zs == nullptr && have && l == 0 && !valid) {
-      p.status[di] = ESPGPU_EINVAL;
-      if (want_trl) p.trailer[di] = 0;
+      esp_at_st(CHK_STATUS, p.status, di, ESPGPU_EINVAL);
+      if (want_trl) esp_at_st(CHK_TRAILER, p.trailer, di, 0);
     }
     return;
   }
@@ -1112,9 +1113,9 @@ __device__ __forceinline__ void tag_group(const GcmParams &p, const uint8_t *lds
       if (mlen == 16) {
         tag = ld16(rec + len - mlen);
       } else {
-        tag.x = q[0];
-        tag.y = q[1];
-        if (mlen > 8) tag.z = q[2];
+        tag.x = esp_ld4w(q, 0);
+        tag.y = esp_ld4w(q, 1);
+        if (mlen > 8) tag.z = esp_ld4w(q, 2);
       }
     }
   }
@@ -1132,8 +1133,8 @@ __device__ __forceinline__ void tag_group(const GcmParams &p, const uint8_t *lds
     }
   }
   if (have && l == 0) {
-    p.status[di] = !valid ? ESPGPU_EINVAL : (ok ? ESPGPU_OK : ESPGPU_EBADMSG);
-    if (want_trl && !(valid && ok)) p.trailer[di] = 0;
+    esp_at_st(CHK_STATUS, p.status, di, !valid ? ESPGPU_EINVAL : (ok ? ESPGPU_OK : ESPGPU_EBADMSG));
+    if (want_trl && !(valid && ok)) esp_at_st(CHK_TRAILER, p.trailer, di, 0);
   }
 }
 
@@ -1141,7 +1142,7 @@ __device__ __forceinline__ void tag_group(const GcmParams &p, const uint8_t *lds
 // per record, burst kernel decrypt, after the ctr pass wrote E_K(J0) and the
 // trailer word): verify, status, trailer word zeroed on failure.
 __device__ __forceinline__ void tag_finish(const GcmParams &p, uint32_t di, uint32_t sa, uint32_t mlen, uint4 Z) {
-  const uint4 dv = *reinterpret_cast<const uint4 *>(p.desc + di);
+  const uint4 dv = esp_desc_ld16(p.desc, di);
   const uint32_t len = dv.y & 0xffffu;
   const int ct_len = (int)len - 16 - (int)mlen;
   const bool valid = ((dv.y >> 16) == sa) && ct_len > 0 && (len & 3) == 0;
@@ -1153,15 +1154,15 @@ __device__ __forceinline__ void tag_finish(const GcmParams &p, uint32_t di, uint
     if (mlen == 16) {
       tag = ld16(rec + len - mlen);
     } else {
-      tag.x = q[0];
-      tag.y = q[1];
-      if (mlen > 8) tag.z = q[2];
+      tag.x = esp_ld4w(q, 0);
+      tag.y = esp_ld4w(q, 1);
+      if (mlen > 8) tag.z = esp_ld4w(q, 2);
     }
     const uint4 d = mask_block(xor4(xor4(Z, p.ej0[di]), tag), (int)mlen);
     ok = ((d.x | d.y | d.z | d.w) == 0);
   }
-  p.status[di] = !valid ? ESPGPU_EINVAL : (ok ? ESPGPU_OK : ESPGPU_EBADMSG);
-  if (p.trailer && !(valid && ok)) p.trailer[di] = 0;
+  esp_at_st(CHK_STATUS, p.status, di, !valid ? ESPGPU_EINVAL : (ok ? ESPGPU_OK : ESPGPU_EBADMSG));
+  if (p.trailer && !(valid && ok)) esp_at_st(CHK_TRAILER, p.trailer, di, 0);
 }
 
 // Self-staging prologue of one chunk (gcm_kernel<..., STAGE>): copies the
@@ -1243,9 +1244,9 @@ __global__ __launch_bounds__(WG) void gcm_kernel(GcmParams p) {
       count = min(p.chunk, p.n - start);
       if (STAGE) stage_in<WG>(p, start, count, s_xout);
       GCM_PHASE(3, it == 0);
-      sa = p.desc[start].sa;
+      sa = esp_at_ptr(CHK_DESC, p.desc, start)->sa;
     } else {
-      const Chunk ch = p.chunks[c];
+      const Chunk ch = esp_at_ld(CHK_CHUNKS, p.chunks, c);
       sa = ch.sa;
       start = ch.start;
       count = ch.count;
@@ -1254,7 +1255,7 @@ __global__ __launch_bounds__(WG) void gcm_kernel(GcmParams p) {
     if (sa != cur_sa) {
       __syncthreads();
       if (sa < p.nsas) {
-        const DevSA *s = p.sas + sa;
+        const DevSA *s = esp_at_ptr(CHK_SAS, p.sas, sa);
         nr = s->nr;
         flags = s->flags;
         mlen = s->mlen;
@@ -1279,7 +1280,7 @@ __global__ __launch_bounds__(WG) void gcm_kernel(GcmParams p) {
       const uint32_t rl = sub + (uint32_t)wave * RPW + (uint32_t)((tid & 63) / S);
       const bool have = rl < count;
       const uint32_t pos = start + (have ? rl : 0);
-      const uint32_t di = p.order ? p.order[pos] : pos;
+      const uint32_t di = p.order ? esp_at_ld(CHK_ORDER, p.order, pos) : pos;
       // Session check per record: a chunk is one session (planner), but a
       // caller-grouped batch (implicit chunks) is trusted only this far: a
       // record whose own session is not this chunk's AEAD session is EINVAL
@@ -1287,17 +1288,17 @@ __global__ __launch_bounds__(WG) void gcm_kernel(GcmParams p) {
       // DIGEST (AH) record, which the ETA / digest kernel owns.
       if (mode != ESPGPU_CSP_MODE_AEAD) {
         if (have && (tid & (S - 1)) == 0) {
-          const uint32_t rsa = p.desc[di].sa;
-          const bool eta = rsa < p.nsas && (p.sas[rsa].mode == ESPGPU_CSP_MODE_ETA ||
-                                          p.sas[rsa].mode == ESPGPU_CSP_MODE_DIGEST);
+          const uint32_t rsa = esp_at_ptr(CHK_DESC, p.desc, di)->sa;
+          const bool eta = rsa < p.nsas && (esp_at_ptr(CHK_SAS, p.sas, rsa)->mode == ESPGPU_CSP_MODE_ETA ||
+                                          esp_at_ptr(CHK_SAS, p.sas, rsa)->mode == ESPGPU_CSP_MODE_DIGEST);
           if (!eta) {
-            p.status[di] = ESPGPU_EINVAL;
-            if (MODE != 1 && p.trailer) p.trailer[di] = 0;
+            esp_at_st(CHK_STATUS, p.status, di, ESPGPU_EINVAL);
+            if (MODE != 1 && p.trailer) esp_at_st(CHK_TRAILER, p.trailer, di, 0);
           }
         }
         continue;
       }
-      do_group<MODE, S>(p, lds, di, have, sa, flags, mlen, (int)nr, (rkptr)(const void *)(p.sas[sa].rk));
+      do_group<MODE, S>(p, lds, di, have, sa, flags, mlen, (int)nr, (rkptr)(const void *)(esp_at_ptr(CHK_SAS, p.sas, sa)->rk));
     }
     GCM_PHASE(5, it == 0);
     if (STAGE) {
@@ -1306,7 +1307,7 @@ __global__ __launch_bounds__(WG) void gcm_kernel(GcmParams p) {
       // (spans from LDS: no host read on the way out, the writes are posted)
       for (uint32_t r = (uint32_t)wave; r < count; r += (uint32_t)(WG / 64)) {
         const uint32_t di = start + r;
-        const uint8_t st = p.status[di];
+        const uint8_t st = esp_at_ld(CHK_STATUS, p.status, di);
         if ((tid & 63) == 0) p.hstat[di] = st;
         if (st == ESPGPU_OK) {
 #pragma unroll
@@ -1362,12 +1363,12 @@ __device__ __forceinline__ void burst_chunk(const GcmParams &p, uint8_t *lds, ui
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
   if (STAGE) stage_in<WG>(p, start, count, s_xout);
-  if (sa == 0xffffffffu) sa = p.desc[start].sa;
+  if (sa == 0xffffffffu) sa = esp_at_ptr(CHK_DESC, p.desc, start)->sa;
   sa = __builtin_amdgcn_readfirstlane(sa);
   if (sa != ss.cur) {
     __syncthreads();
     if (sa < p.nsas) {
-      const DevSA *s = p.sas + sa;
+      const DevSA *s = esp_at_ptr(CHK_SAS, p.sas, sa);
       ss.nr = s->nr;
       ss.flags = s->flags;
       ss.mlen = s->mlen;
@@ -1386,24 +1387,24 @@ __device__ __forceinline__ void burst_chunk(const GcmParams &p, uint8_t *lds, ui
     // as gcm_kernel: EINVAL unless the ETA / digest kernel's record
     for (uint32_t r = (uint32_t)tid; r < count; r += WG) {
       const uint32_t pos = start + r;
-      const uint32_t di = p.order ? p.order[pos] : pos;
-      const uint32_t rsa = p.desc[di].sa;
-      const bool eta = rsa < p.nsas && (p.sas[rsa].mode == ESPGPU_CSP_MODE_ETA ||
-                                          p.sas[rsa].mode == ESPGPU_CSP_MODE_DIGEST);
+      const uint32_t di = p.order ? esp_at_ld(CHK_ORDER, p.order, pos) : pos;
+      const uint32_t rsa = esp_at_ptr(CHK_DESC, p.desc, di)->sa;
+      const bool eta = rsa < p.nsas && (esp_at_ptr(CHK_SAS, p.sas, rsa)->mode == ESPGPU_CSP_MODE_ETA ||
+                                          esp_at_ptr(CHK_SAS, p.sas, rsa)->mode == ESPGPU_CSP_MODE_DIGEST);
       if (!eta) {
-        p.status[di] = ESPGPU_EINVAL;
-        if (DIR == 0 && p.trailer) p.trailer[di] = 0;
+        esp_at_st(CHK_STATUS, p.status, di, ESPGPU_EINVAL);
+        if (DIR == 0 && p.trailer) esp_at_st(CHK_TRAILER, p.trailer, di, 0);
       }
     }
     if (STAGE) {
       // the statuses go back to the host (no results: nothing verified)
       __syncthreads();
-      for (uint32_t r = (uint32_t)tid; r < count; r += WG) p.hstat[start + r] = p.status[start + r];
+      for (uint32_t r = (uint32_t)tid; r < count; r += WG) p.hstat[start + r] = esp_at_ld(CHK_STATUS, p.status, start + r);
     }
     return;
   }
   GCM_PHASE(3, first);
-  const rkptr rk = (rkptr)(const void *)(p.sas[sa].rk);
+  const rkptr rk = (rkptr)(const void *)(esp_at_ptr(CHK_SAS, p.sas, sa)->rk);
   constexpr uint32_t kCtrRpw = 64 / kBurstCtrLanes, kTagRpw = 64 / ST;
   if (DIR == 0) {
     constexpr uint32_t kCw = kBurstCtrWaves, kTw = WG / 64 - kBurstCtrWaves;
@@ -1412,7 +1413,7 @@ __device__ __forceinline__ void burst_chunk(const GcmParams &p, uint8_t *lds, ui
         const uint32_t rl = sub + (uint32_t)wave * kCtrRpw + (uint32_t)((tid & 63) / kBurstCtrLanes);
         const bool have = rl < count;
         const uint32_t pos = start + (have ? rl : 0);
-        const uint32_t di = p.order ? p.order[pos] : pos;
+        const uint32_t di = p.order ? esp_at_ld(CHK_ORDER, p.order, pos) : pos;
         if (__any(have)) ctr_group<0, kBurstCtrLanes, true>(p, lds, di, have, sa, mlen, (int)nr, rk, LDS_TP);
       }
     } else {
@@ -1420,7 +1421,7 @@ __device__ __forceinline__ void burst_chunk(const GcmParams &p, uint8_t *lds, ui
         const uint32_t rl = sub + ((uint32_t)wave - kCw) * kTagRpw + (uint32_t)((tid & 63) / ST);
         const bool have = rl < count;
         const uint32_t pos = start + (have ? rl : 0);
-        const uint32_t di = p.order ? p.order[pos] : pos;
+        const uint32_t di = p.order ? esp_at_ld(CHK_ORDER, p.order, pos) : pos;
         if (__any(have)) tag_group<0, ST>(p, lds, di, have, sa, flags, mlen, s_z, rl);
       }
     }
@@ -1429,7 +1430,7 @@ __device__ __forceinline__ void burst_chunk(const GcmParams &p, uint8_t *lds, ui
     GCM_PHASE(5, first);
     for (uint32_t r = (uint32_t)tid; r < count; r += WG) {
       const uint32_t pos = start + r;
-      tag_finish(p, p.order ? p.order[pos] : pos, sa, mlen, s_z[r]);
+      tag_finish(p, p.order ? esp_at_ld(CHK_ORDER, p.order, pos) : pos, sa, mlen, s_z[r]);
     }
     // s_z is rewritten by the next chunk's hash waves
     __syncthreads();
@@ -1438,7 +1439,7 @@ __device__ __forceinline__ void burst_chunk(const GcmParams &p, uint8_t *lds, ui
       const uint32_t rl = sub + (uint32_t)wave * kCtrRpw + (uint32_t)((tid & 63) / kBurstCtrLanes);
       const bool have = rl < count;
       const uint32_t pos = start + (have ? rl : 0);
-      const uint32_t di = p.order ? p.order[pos] : pos;
+      const uint32_t di = p.order ? esp_at_ld(CHK_ORDER, p.order, pos) : pos;
       if (__any(have)) ctr_group<1, kBurstCtrLanes, true>(p, lds, di, have, sa, mlen, (int)nr, rk, LDS_TP);
     }
     // the ciphertext and E_K(J0) written above are read below by other waves
@@ -1447,7 +1448,7 @@ __device__ __forceinline__ void burst_chunk(const GcmParams &p, uint8_t *lds, ui
       const uint32_t rl = sub + (uint32_t)wave * kTagRpw + (uint32_t)((tid & 63) / ST);
       const bool have = rl < count;
       const uint32_t pos = start + (have ? rl : 0);
-      const uint32_t di = p.order ? p.order[pos] : pos;
+      const uint32_t di = p.order ? esp_at_ld(CHK_ORDER, p.order, pos) : pos;
       if (__any(have)) tag_group<1, ST>(p, lds, di, have, sa, flags, mlen);
     }
   }
@@ -1456,7 +1457,7 @@ __device__ __forceinline__ void burst_chunk(const GcmParams &p, uint8_t *lds, ui
     __syncthreads();
     for (uint32_t r = (uint32_t)wave; r < count; r += (uint32_t)(WG / 64)) {
       const uint32_t di = start + r;
-      const uint8_t st = p.status[di];
+      const uint8_t st = esp_at_ld(CHK_STATUS, p.status, di);
       if ((tid & 63) == 0) p.hstat[di] = st;
       if (st == ESPGPU_OK) {
 #pragma unroll
@@ -1505,7 +1506,7 @@ __global__ __launch_bounds__(WG) void gcm_burst_kernel(GcmParams p) {
       const uint32_t start = c * p.chunk;
       burst_chunk<DIR, WG, STAGE>(p, lds, start, min(p.chunk, p.n - start), 0xffffffffu, ss, s_z, s_xout, it == 0);
     } else {
-      const Chunk ch = p.chunks[c];
+      const Chunk ch = esp_at_ld(CHK_CHUNKS, p.chunks, c);
       burst_chunk<DIR, WG, STAGE>(p, lds, ch.start, ch.count, ch.sa, ss, s_z, s_xout, it == 0);
     }
   }
@@ -1684,6 +1685,12 @@ int set_gcm_opts(uint32_t opts) {
 }
 
 int launch_gcm_door(const DoorArgs &a, int grid, void *stream) {
+#ifdef ESPGPU_BOUNDS
+  // the doorbell kernel builds its parameters on the device and runs beside
+  // other launches: it is not checked (an empty block checks nothing)
+  const ChkArm none{};
+  ESPGPU_CHK_SET(none, reinterpret_cast<hipStream_t>(stream));
+#endif
   hipLaunchKernelGGL((gcm_door_kernel<kBurstWG>), dim3(grid), dim3(kBurstWG), 0,
                      reinterpret_cast<hipStream_t>(stream), a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -1712,6 +1719,9 @@ int launch_gcm(const GcmParams &pp, int encrypt, int in_place, int grid, int lan
   while (p.chunk < per && p.chunk < (uint32_t)kChunkRecs) p.chunk <<= 1;
   if (p.chunks == nullptr) grid = std::max(1, std::min(grid, (int)((p.n + p.chunk - 1) / p.chunk)));
   if (!small && p.ej0 != nullptr) return -1;          // (the burst design serves small batches only)
+#ifdef ESPGPU_BOUNDS
+  ESPGPU_CHK_SET(p.chk, st);
+#endif
   if (burst) {
     if (p.xin != nullptr && p.chunks != nullptr) return -1;   // self-staging: implicit chunks only
     if (p.xin != nullptr && encrypt)

@@ -471,6 +471,9 @@ int launch_fused(espgpu_ctx *c, Slot &s, uint8_t *dres) {
   s.timed = GPU_TIME_SMALL;
   if (s.timed) hipEventRecord(s.k0, s.st);
   s.wq = s.st;                                     // the kernel writes results to host memory
+#ifdef ESPGPU_BOUNDS
+  espgpu_chk_arm(c, s.d_arena, s.bytes, s.op ? nullptr : s.d_out, s.bytes, 16);
+#endif
   e = run_batch(c, s.d_arena, reinterpret_cast<const espgpu_desc *>(s.d_arena + s.desc_off), s.nrec,
                 dres + s.stat_off, s.op ? nullptr : s.d_out, (uint32_t)ESPGPU_BATCH_GROUPED, s.op, s.st,
                 nullptr, 1u, &stg);
@@ -540,6 +543,9 @@ int launch_copy(espgpu_ctx *c, Slot &s, bool small, bool kcopy, uint8_t *dres) {
   if (s.timed) hipEventRecord(s.k0, s_k);
   // a single-session batch skips the device planner (ESPGPU_BATCH_GROUPED:
   // one session trivially satisfies "one session per chunk")
+#ifdef ESPGPU_BOUNDS
+  espgpu_chk_arm(c, s.d_arena, s.bytes, s.op ? nullptr : s.d_out, s.bytes, 16);
+#endif
   e = run_batch(c, s.d_arena, reinterpret_cast<const espgpu_desc *>(s.d_arena + s.desc_off), s.nrec,
                 dres + s.stat_off, s.op ? nullptr : s.d_out, s.mixed ? 0u : (uint32_t)ESPGPU_BATCH_GROUPED,
                 s.op, s_k, nullptr, s.kinds);
@@ -746,6 +752,9 @@ void espgpu_fini(espgpu_ctx *c) {
   }
   hipFree(c->d_sas); hipFree(c->d_gtab); hipFree(c->d_tpair); hipFree(c->d_dpair); hipFree(c->d_isbox);
   hipFree(c->d_queue);
+#ifdef ESPGPU_BOUNDS
+  hipFree(c->chk.rep);
+#endif
   hipFree(c->d_ej0);
   hipFree(c->d_work); hipFree(c->d_order); hipFree(c->d_chunks); hipFree(c->d_nchunks);
   hipFree(c->d_stage_ws);

@@ -46,6 +46,35 @@ int launch_end(espgpu_ctx *c, hipStream_t st) {
   return 0;
 }
 
+#ifdef ESPGPU_BOUNDS
+int chk_report_reset(espgpu_ctx *c) {
+  if (!c->chk.rep) {
+    HIPCHK(c, hipMalloc(&c->chk.rep, sizeof(ChkReport)));
+  }
+  ChkReport zero{};
+  zero.hw[0] = zero.hw[1] = kChkNoMark;
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy(c->chk.rep, &zero, sizeof zero, hipMemcpyHostToDevice));
+  return 0;
+}
+
+// What the launches of one run_batch are checked against: the armed extents
+// (consumed) or none, and the index bounds run_batch knows.
+int chk_take(espgpu_ctx *c, uint32_t n, uint32_t nsas, uint32_t nchunks, ChkArm *out) {
+  if (!c->chk.rep) {
+    int e = chk_report_reset(c);
+    if (e) return e;
+  }
+  if (!c->chk_armed) c->chk.lo[0] = c->chk.lo[1] = c->chk.hi[0] = c->chk.hi[1] = 0;
+  c->chk_armed = false;
+  c->chk.n = n;
+  c->chk.nsas = nsas;
+  c->chk.nchunks = nchunks;
+  *out = c->chk;
+  return 0;
+}
+#endif
+
 }  // namespace
 
 // Launch the crypto kernels for one batch of device-resident records.
@@ -101,6 +130,9 @@ int run_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32
     p.chunks = c->d_chunks;
     p.nchunks = c->d_nchunks;
   }
+#ifdef ESPGPU_BOUNDS
+  if ((e = chk_take(c, n, nsas, p.chunks ? c->max_chunks : 0u, &p.chk))) return e;
+#endif
   const int in_place = (!encrypt && p.out == d_arena);
   // E_K(J0) scratch: the burst kernel (small batches of <= gcm_burst records,
   // out of place or encrypt; launch_gcm picks the kernel from it)
@@ -167,6 +199,9 @@ int run_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, uint32
     g.status = d_status;
     g.nsas = nsas;
     g.op = (kinds & 4) ? 2u : (encrypt ? 1u : 0u);
+#ifdef ESPGPU_BOUNDS
+    g.chk = p.chk;
+#endif
     if (launch_digest(g, c->n_dig > c->n_dig_wide, c->n_dig_wide > 0, grid, st))
       return fail(c, ESPGPU_EIO, "digest kernel launch failed");
   }
@@ -242,6 +277,9 @@ int host_pipeline(espgpu_ctx *c, const uint8_t *h_arena, uint64_t arena_bytes,
       lo = std::min(lo, o);
       hi = std::max(hi, o + h_desc[i].len);
     }
+#ifdef ESPGPU_BOUNDS
+    espgpu_chk_arm(c, c->e2e_arena + lo, hi - lo, encrypt ? nullptr : c->e2e_out + lo, hi - lo, 16);
+#endif
     hi = std::min(arena_bytes, hi + 16);                 // partial-block loads read <= 16 B past
     hipEvent_t ein = c->e2e_in[k & 1], ek = c->e2e_k[k & 1];
     HIPCHK(c, hipMemcpyAsync(c->e2e_desc + i0, h_desc + i0, m * sizeof(espgpu_desc), hipMemcpyHostToDevice, c->s_in));
@@ -504,5 +542,34 @@ int espgpu_decrypt_host(espgpu_ctx *c, const uint8_t *h_arena, uint64_t arena_by
     return fail(c, ESPGPU_ENOTSUP, "the host pipeline does not serve contexts with DIGEST sessions");
   return batch_rc(c, host_pipeline(c, h_arena, arena_bytes, h_desc, n, h_status, h_out, chunk, flags, 0));
 }
+
+#ifdef ESPGPU_BOUNDS
+// ---- the bounds-checked build (espgpu_internal.h, bounds_chk.h) ----------------
+__attribute__((visibility("default"))) int espgpu_chk_arm(espgpu_ctx *c, const void *arena_base,
+                                                          uint64_t arena_bytes, const void *out_base,
+                                                          uint64_t out_bytes, uint32_t pad) {
+  if (!c || !arena_base) return ESPGPU_EINVAL;
+  c->chk.lo[0] = (uint64_t)(uintptr_t)arena_base;
+  c->chk.hi[0] = c->chk.lo[0] + arena_bytes;
+  c->chk.lo[1] = out_base ? (uint64_t)(uintptr_t)out_base : c->chk.lo[0];
+  c->chk.hi[1] = out_base ? c->chk.lo[1] + out_bytes : c->chk.hi[0];
+  c->chk.pad = pad;
+  c->chk_armed = true;
+  return 0;
+}
+
+__attribute__((visibility("default"))) int espgpu_chk_report(espgpu_ctx *c, void *buf, uint32_t cap) {
+  if (!c || !buf) return -ESPGPU_EINVAL;
+  if (!c->chk.rep && chk_report_reset(c)) return -ESPGPU_EIO;
+  if (hipDeviceSynchronize() != hipSuccess) return -ESPGPU_EIO;
+  const uint32_t nb = std::min<uint32_t>(cap, (uint32_t)sizeof(ChkReport));
+  if (hipMemcpy(buf, c->chk.rep, nb, hipMemcpyDeviceToHost) != hipSuccess) return -ESPGPU_EIO;
+  return (int)nb;
+}
+
+__attribute__((visibility("default"))) int espgpu_chk_reset(espgpu_ctx *c) {
+  return c ? chk_report_reset(c) : ESPGPU_EINVAL;
+}
+#endif
 
 }  // extern "C"

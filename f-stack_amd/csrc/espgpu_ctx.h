@@ -240,6 +240,12 @@ struct espgpu_ctx {
   espgpu_stats stats{};
   float last_ms = 0.f;
   std::string err;
+#ifdef ESPGPU_BOUNDS
+  // the bounds-checked build (bounds_chk.h): the report in device memory
+  // (allocated at the first launch) and the extents armed for the next one
+  espgpu::ChkArm chk{};
+  bool chk_armed = false;
+#endif
 };
 
 namespace espgpu {

@@ -5,6 +5,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "bounds_chk.h"
 #include "espgpu.h"
 #include "req_shape.h"
 
@@ -97,6 +98,9 @@ struct GcmParams {
   // decrypt out of place: 0 = plaintext at the record's own offset in out;
   // else record i's plaintext at out + i * out_stride (espgpu_decrypt_batch_packed)
   uint32_t out_stride;
+#ifdef ESPGPU_BOUNDS
+  ChkArm chk;                     // what this launch is checked against (bounds_chk.h)
+#endif
 };
 
 // Work-queue regions (ctx d_queue): one per kernel family, kQueueRegionWords
@@ -143,6 +147,9 @@ struct DigestParams {
   // 2: driver path, swcr_authcompute to the letter: the record hashed as it
   //    stands; per record compute, or verify if desc.salt has kDigVerifyBit
   uint32_t op;
+#ifdef ESPGPU_BOUNDS
+  ChkArm chk;
+#endif
 };
 
 // esp_input_cb's checks on the last 3 plaintext bytes (xform_esp.c:597-630),
@@ -268,6 +275,23 @@ int launch_esp_encap(uint8_t *arena, const espgpu_pkt *pkt, const uint16_t *sa, 
                      uint8_t *estatus, void *stream);
 int launch_esp_sent(const espgpu_pkt *opkt, const espgpu_desc *desc, const uint8_t *status, uint32_t n,
                     espgpu_encsa *enc, uint32_t nenc, void *stream);
+#ifdef ESPGPU_BOUNDS
+// The bounds-checked build's host side (`make checked` only: libespgpu.so
+// exports none of it and include/espgpu.h does not declare it; bounds_chk.h).
+// arm: the byte extents the ctx's NEXT run_batch is checked against (arena,
+// and out for an out-of-place decrypt; out_base nullptr = the arena's), reads
+// allowed to end `pad` bytes past an extent, writes not past it.  One launch
+// consumes the arming; a launch that was not armed checks indices only.
+// report: up to cap bytes of the ChkReport so far (after a synchronisation of
+// the ctx's launches); -> the bytes written, negative on failure.
+// reset: the report starts again (counts zero, marks kChkNoMark).
+extern "C" {
+int espgpu_chk_arm(espgpu_ctx *ctx, const void *arena_base, uint64_t arena_bytes, const void *out_base,
+                   uint64_t out_bytes, uint32_t pad);
+int espgpu_chk_report(espgpu_ctx *ctx, void *buf, uint32_t cap);
+int espgpu_chk_reset(espgpu_ctx *ctx);
+}
+#endif
 int launch_xfer(const XferSpan *spans, uint32_t nspans, const uint8_t *status, void *stream);
 int launch_replay_merge(uint8_t *status, const uint8_t *rstatus, uint32_t n, void *stream);
 int launch_plan(const espgpu_desc *d_desc, uint32_t n, const DevSA *sas, uint32_t nsas, uint32_t cap_sas,
