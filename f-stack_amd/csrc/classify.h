@@ -21,6 +21,8 @@ ESPGPU_HD inline uint32_t key_u32hash(uint32_t spi) {
   return h;
 }
 
+constexpr uint32_t kClsKnown = ESPGPU_CLS_IPCSUM | 0xffff0000u;   // and ESPGPU_CLS_NATT_PORT's bits
+
 ESPGPU_HD inline uint32_t cls_bswap32(uint32_t x) { return __builtin_bswap32(x); }
 // the big-endian 16-bit field in the low / the high half of a memory-order dword
 ESPGPU_HD inline uint32_t cls_be16lo(uint32_t w) { return ((w & 0xffu) << 8) | ((w >> 8) & 0xffu); }
@@ -54,9 +56,12 @@ ESPGPU_HD inline ClsSlotHead cls_slot_head(const espgpu_sad_entry *e) {
 // Probe from the SPI's home slot to a match or a free slot, at most nslots
 // steps (key_allocsa, key.c:1091-1133: the SPI first, then protocol, family
 // and destination).  dst[] is the packet's destination in memory-order
-// dwords, one for af 4 and four for af 6.  True: *sa and *salt are the entry's.
-ESPGPU_HD inline bool cls_lookup(const espgpu_sad_entry *table, uint32_t nslots, uint32_t spi, uint32_t af,
-                                 const uint32_t dst[4], uint32_t *sa, uint32_t *salt) {
+// dwords, one for af 4 and four for af 6.  True: *sa and *salt are the entry's,
+// *eflags its flags and, for an ESPGPU_SAD_NATT entry, *ports its dst[4..7]
+// (natt->sport, natt->dport as they lie in a UDP header's first dword).
+ESPGPU_HD inline bool cls_find(const espgpu_sad_entry *table, uint32_t nslots, uint32_t spi, uint32_t af,
+                               const uint32_t dst[4], uint32_t *sa, uint32_t *salt, uint32_t *eflags,
+                               uint32_t *ports) {
   if (spi == 0) return false;
   const uint32_t mask = nslots - 1;
   uint32_t slot = key_u32hash(spi) & mask;
@@ -71,9 +76,17 @@ ESPGPU_HD inline bool cls_lookup(const espgpu_sad_entry *table, uint32_t nslots,
       if (mem_ld32(ed + 4 * j) != dst[j]) return false;
     *sa = h.ids & 0xffffu;
     *salt = h.salt;
+    *eflags = h.flags;
+    *ports = (h.flags & ESPGPU_SAD_NATT) ? mem_ld32(ed + 4) : 0u;
     return true;
   }
   return false;
+}
+
+ESPGPU_HD inline bool cls_lookup(const espgpu_sad_entry *table, uint32_t nslots, uint32_t spi, uint32_t af,
+                                 const uint32_t dst[4], uint32_t *sa, uint32_t *salt) {
+  uint32_t eflags, ports;
+  return cls_find(table, nslots, spi, af, dst, sa, salt, &eflags, &ports);
 }
 
 // espgpu_esp_classify's rule; *desc is written in every case.  `table` usable
@@ -82,6 +95,7 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
                                        uint32_t len, uint32_t off4, uint32_t flags, espgpu_desc *desc) {
   int st = ESPGPU_EINVAL;
   uint32_t skip = 0, rlen = 0, af = 0, spi = 0, sa = 0, salt = 0, dst[4] = {0, 0, 0, 0};
+  uint32_t udp = 0, uports = 0;                        // a UDP-encapsulated packet and its port dword
   do {
     if (len < 20) break;
     // the 20 bytes every packet has, in one round of loads
@@ -106,14 +120,36 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
       if (ip_len < hlen || ip_len > len) break;
       st = ESPGPU_ENOTSUP;
       if (cls_be16hi(w1) & 0x3fffu) break;             // IP_MF | IP_OFFMASK, :807
-      if (((w2 >> 8) & 0xffu) != 50) break;            // ip_p
-      st = ESPGPU_EINVAL;
-      if (ip_len - hlen < 8) break;                    // ipsec_input.c:141
-      if (ip_len & 3) break;                           // xform_esp.c:279
-      af = 4;
-      skip = hlen;
-      rlen = ip_len - hlen;
-      dst[0] = w4;
+      const uint32_t ip_p = (w2 >> 8) & 0xffu, port = flags >> 16;
+      if (ip_p == 17 && port) {
+        // udp_input up to the UF_ESPINUDP socket, then udp_ipsec_input
+        if (ip_len - hlen < 8) break;                  // no UDP header: an ordinary datagram's error
+        uports = mem_ld32(pkt + hlen);
+        const uint32_t u1 = mem_ld32(pkt + hlen + 4), ulen = cls_be16lo(u1);
+        if (cls_be16hi(uports) != port) break;         // another socket's, udp_usrreq.c:335
+        st = ESPGPU_EINVAL;
+        if (ulen < 8 || ulen > ip_len - hlen) break;   // :468-472; a longer ip_len is trimmed, :474
+        st = ESPGPU_ENOTSUP;
+        if (u1 >> 16) break;                           // uh_sum: udp_input verifies it, :489-520
+        if (ulen - 8 < 8) break;                       // the keepalive, udpencap.c:131-132
+        if (mem_ld32(pkt + hlen + 8) == 0) break;      // the non-ESP marker, :135
+        st = ESPGPU_EINVAL;
+        if ((ulen - 8) & 3) break;                     // xform_esp.c:279
+        udp = 1;
+        af = 4;
+        skip = hlen + 8;
+        rlen = ulen - 8;
+        dst[0] = w4;
+      } else {
+        if (ip_p != 50) break;
+        st = ESPGPU_EINVAL;
+        if (ip_len - hlen < 8) break;                  // ipsec_input.c:141
+        if (ip_len & 3) break;                         // xform_esp.c:279
+        af = 4;
+        skip = hlen;
+        rlen = ip_len - hlen;
+        dst[0] = w4;
+      }
     } else if (ver == 6) {                             // ip6_input, ipsec6_input
       if (len < 40) break;
       const uint32_t plen = cls_be16lo(w1);
@@ -134,7 +170,14 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
       break;
     }
     spi = cls_bswap32(mem_ld32(pkt + skip));
-    st = cls_lookup(table, nslots, spi, af, dst, &sa, &salt) ? 0 : ESPGPU_ENOENT;
+    uint32_t eflags = 0, eports = 0;
+    st = cls_find(table, nslots, spi, af, dst, &sa, &salt, &eflags, &eports) ? 0 : ESPGPU_ENOENT;
+    if (st == 0 && udp) {                              // udpencap.c:173-181
+      if (!(eflags & ESPGPU_SAD_NATT) || eports != uports) st = ESPGPU_ENOENT;
+    } else if (st == 0 && (eflags & ESPGPU_SAD_NATT)) {
+      // the later steps tell a UDP-encapsulated packet by its SA alone: the host's
+      st = ESPGPU_ENOTSUP;
+    }
   } while (0);
   espgpu_desc d;
   d.off4 = st ? off4 : off4 + skip / 4;
@@ -153,10 +196,13 @@ inline int sad_build(const espgpu_sad_entry *sas, uint32_t nsas, espgpu_sad_entr
   const uint32_t mask = nslots - 1;
   for (uint32_t i = 0; i < nsas; ++i) {
     const espgpu_sad_entry &e = sas[i];
-    if (e.spi == 0 || (e.proto != 50 && e.proto != 51) || (e.af != 4 && e.af != 6) || e.flags != 0)
+    if (e.spi == 0 || (e.proto != 50 && e.proto != 51) || (e.af != 4 && e.af != 6) ||
+        (e.flags & ~(uint32_t)ESPGPU_SAD_NATT))
       return ESPGPU_EINVAL;
+    const bool natt = e.flags & ESPGPU_SAD_NATT;
+    if (natt && (e.proto != 50 || e.af != 4)) return ESPGPU_EINVAL;      // udpencap.c:155-163
     if (e.af == 4)
-      for (int k = 4; k < 16; ++k)
+      for (int k = natt ? 8 : 4; k < 16; ++k)
         if (e.dst[k]) return ESPGPU_EINVAL;
     uint32_t slot = key_u32hash(e.spi) & mask;
     while (table[slot].spi != 0) {                     // a free slot exists: nslots >= 2 * nsas

@@ -13,7 +13,8 @@
 
 namespace espgpu {
 
-constexpr uint32_t kInKnown = ESPGPU_IN_TRANSPORT | ESPGPU_IN_TUNNEL | ESPGPU_IN_PAD_RAND | ESPGPU_IN_AF6;
+constexpr uint32_t kInKnown =
+    ESPGPU_IN_TRANSPORT | ESPGPU_IN_TUNNEL | ESPGPU_IN_PAD_RAND | ESPGPU_IN_AF6 | ESPGPU_IN_NATT;
 
 // a 16-bit value as the big-endian field in one half of a memory-order dword
 ESPGPU_HD inline uint32_t dcp_be16(uint32_t x) { return ((x & 0xffu) << 8) | ((x >> 8) & 0xffu); }
@@ -31,9 +32,11 @@ ESPGPU_HD inline int dcp_plan(uint32_t flags, uint32_t hlen, uint32_t alen, uint
                               uint32_t trailer, DecapPlan *p) {
   const uint32_t mode = flags & (ESPGPU_IN_TRANSPORT | ESPGPU_IN_TUNNEL);
   const bool af6 = flags & ESPGPU_IN_AF6;
-  if ((flags & ~kInKnown) || mode == (ESPGPU_IN_TRANSPORT | ESPGPU_IN_TUNNEL)) return ESPGPU_EINVAL;
+  // a NAT-T SA's skip holds the 8 UDP bytes behind the IP header (udpencap.c:196)
+  const uint32_t u = (flags & ESPGPU_IN_NATT) ? 8u : 0u;
+  if ((flags & ~kInKnown) || mode == (ESPGPU_IN_TRANSPORT | ESPGPU_IN_TUNNEL) || (u && af6)) return ESPGPU_EINVAL;
   if (skip & 3) return ESPGPU_EINVAL;
-  if (af6 ? skip != 40 : (skip < 20 || skip > 60)) return ESPGPU_EINVAL;
+  if (af6 ? skip != 40 : (skip < 20 + u || skip > 60 + u)) return ESPGPU_EINVAL;
   if ((uint64_t)rlen < (uint64_t)hlen + alen + 2) return ESPGPU_EINVAL;          // plen < 2
   const uint32_t plen = rlen - hlen - alen;
   if (!(trailer & ESPGPU_TR_VALID)) return ESPGPU_EINVAL;
@@ -52,20 +55,21 @@ ESPGPU_HD inline int dcp_plan(uint32_t flags, uint32_t hlen, uint32_t alen, uint
     return ESPGPU_EPFNOSUPPORT;
   }
   p->transport = !tunnel;
-  p->off = tunnel ? skip + hlen : hlen;
-  p->len = tunnel ? q : skip + q;
+  p->off = tunnel ? skip + hlen : hlen + u;
+  p->len = tunnel ? q : skip - u + q;
   p->nxt = nxt;
   p->q = q;
   return 0;
 }
 
 // Check 5: the outer header's skip bytes from src to dst + hlen, fixed on the
-// way.  Every dword is loaded before the first is stored: with src == dst the
+// way; for a NAT-T SA its skip - 8 bytes to dst + hlen + 8, over the UDP header.  Every dword is loaded before the first is stored: with src == dst the
 // ranges overlap whenever hlen < skip.  The loops have constant bounds so that
 // the device keeps w[] in registers.
 ESPGPU_HD inline int dcp_transport(const uint8_t *src, uint8_t *dst, uint32_t flags, uint32_t hlen, uint32_t skip,
                                    const DecapPlan &p) {
-  const uint32_t nw = skip / 4;                      // 5 .. 15
+  const uint32_t u = (flags & ESPGPU_IN_NATT) ? 8u : 0u;
+  const uint32_t nw = (skip - u) / 4;                // 5 .. 15
   uint32_t w[15];
 #pragma unroll
   for (uint32_t k = 0; k < 15; ++k) w[k] = k < nw ? mem_ld32(src + 4 * k) : 0u;
@@ -75,7 +79,7 @@ ESPGPU_HD inline int dcp_transport(const uint8_t *src, uint8_t *dst, uint32_t fl
     w[1] = (w[1] & 0xff000000u) | p.nxt << 16 | dcp_be16(p.q & 0xffffu);
   } else {
     if ((w[0] & 0xffu) != (0x40u | nw)) return ESPGPU_EINVAL;
-    w[0] = (w[0] & 0xffffu) | dcp_be16((skip + p.q) & 0xffffu) << 16;            // ip_len, :312
+    w[0] = (w[0] & 0xffffu) | dcp_be16((skip - u + p.q) & 0xffffu) << 16;        // ip_len, :312
     w[2] = (w[2] & 0x000000ffu) | p.nxt << 8;                                    // ip_p; ip_sum = 0, :313
     // in_cksum over the header (:314): the one's-complement sum of the 16-bit
     // words is the same in either byte order up to a byte swap, so the sum of
@@ -91,7 +95,7 @@ ESPGPU_HD inline int dcp_transport(const uint8_t *src, uint8_t *dst, uint32_t fl
   }
 #pragma unroll
   for (uint32_t k = 0; k < 15; ++k)
-    if (k < nw) mem_st32(dst + hlen + 4 * k, w[k]);
+    if (k < nw) mem_st32(dst + hlen + u + 4 * k, w[k]);
   return 0;
 }
 

@@ -70,7 +70,8 @@ __global__ __launch_bounds__(256) void dcp_kernel(DcpArgs a) {
       if (d.sa < a.nin && d.sa < a.nsas &&
           esp_shape_of(a.sas[d.sa].mode, a.sas[d.sa].calg, a.sas[d.sa].mlen, 0, &s)) {
         // a descriptor that is not off4's own gives a skip the rule refuses
-        const uint32_t d4 = d.off4 - p.off4, skip = d4 < 16 ? d4 * 4 : ~0u;
+        // (up to 15 header dwords and a NAT-T SA's two UDP dwords)
+        const uint32_t d4 = d.off4 - p.off4, skip = d4 < 18 ? d4 * 4 : ~0u;
         const size_t at = (size_t)p.off4 * 4;
         DecapPlan pl;
         st = esp_decap_rule(a.in[d.sa].flags, s.ivlen, s.alen, a.arena + at, a.out + at, skip, d.len, tr, &pl);

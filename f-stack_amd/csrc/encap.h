@@ -17,7 +17,8 @@ namespace espgpu {
 
 constexpr uint32_t kEncDf = ESPGPU_ENC_DF_SET | ESPGPU_ENC_DF_COPY;
 constexpr uint32_t kEncEcn = ESPGPU_ENC_ECN_ALLOWED | ESPGPU_ENC_ECN_NOCARE;
-constexpr uint32_t kEncKnown = ESPGPU_ENC_TUNNEL | ESPGPU_ENC_AF6 | kEncDf | kEncEcn | ESPGPU_ENC_RFC6864;
+constexpr uint32_t kEncKnown =
+    ESPGPU_ENC_TUNNEL | ESPGPU_ENC_AF6 | kEncDf | kEncEcn | ESPGPU_ENC_RFC6864 | ESPGPU_ENC_NATT;
 
 // a 16-bit value as the big-endian field in one half of a memory-order dword
 ESPGPU_HD inline uint32_t enc_be16(uint32_t x) { return ((x & 0xffu) << 8) | ((x >> 8) & 0xffu); }
@@ -41,7 +42,7 @@ ESPGPU_HD inline bool enc_linklocal(uint32_t a0) { return (a0 & 0xc0ffu) == 0x80
 
 // The result of an accepted packet (check 7).
 struct EncapOut {
-  uint32_t front;      // hlen + oh: the wire packet starts that far before pkt
+  uint32_t front;      // hlen + oh (+ 8 for a NAT-T SA): the wire packet starts that far before pkt
   uint32_t total;      // the wire packet's length
   uint32_t reclen;     // the ESP record's: the wire packet's last bytes
   uint32_t frame;      // rlen | next header << 16
@@ -56,6 +57,9 @@ ESPGPU_HD inline int esp_encap_rule(const espgpu_encsa *e, const espgpu_eshape &
   const uint32_t f = e->flags;
   if ((f & ~kEncKnown) || (f & kEncDf) == kEncDf || (f & kEncEcn) == kEncEcn) return ESPGPU_EINVAL;
   const bool af6 = f & ESPGPU_ENC_AF6;
+  // udp_ipsec_output's 8 bytes between the IP and the ESP header
+  const uint32_t u = (f & ESPGPU_ENC_NATT) ? 8u : 0u;
+  if (u && af6) return ESPGPU_EAFNOSUPPORT;                                      // udpencap.c:222-223
   uint32_t src[4], dst[4];
 #pragma unroll
   for (uint32_t k = 0; k < 4; ++k) {
@@ -64,6 +68,8 @@ ESPGPU_HD inline int esp_encap_rule(const espgpu_encsa *e, const espgpu_eshape &
   }
   const bool src0 = af6 ? !(src[0] | src[1] | src[2] | src[3]) : !src[0];
   const bool dst0 = af6 ? !(dst[0] | dst[1] | dst[2] | dst[3]) : !dst[0];
+  // natt->sport, natt->dport in dst[4..7], as they lie in the UDP header's first dword
+  if (u && (src[1] | src[2] | src[3] | dst[2] | dst[3])) return ESPGPU_EINVAL;
   if (af6) {
     if (src0 || dst0) return ESPGPU_EINVAL;                                      // ipsec_output.c:961-964
     if (enc_linklocal(src[0]) || enc_linklocal(dst[0])) return ESPGPU_ENOTSUP;   // :975-981 is the host's
@@ -102,7 +108,11 @@ ESPGPU_HD inline int esp_encap_rule(const espgpu_encsa *e, const espgpu_eshape &
   const uint32_t rlen = tunnel ? len : len - skip, padding = esp_padding(rlen, s.blks);
   const uint32_t reclen = hlen + rlen + padding + s.alen, total = (tunnel ? oh : skip) + reclen;
   if (total > 65535) return ESPGPU_EMSGSIZE;                                     // xform_esp.c:747
-  if (hlen + oh > headroom || padding + s.alen > tailroom) return ESPGPU_ENOBUFS;   // :772-780, :810-818
+  // (the reference would let ip_len wrap, udpencap.c:240: refused deliberately)
+  if (total + u > 65535) return ESPGPU_EMSGSIZE;
+  // :772-780, :810-818, udpencap.c:227-231
+  if (hlen + oh + u > headroom || padding + s.alen > tailroom) return ESPGPU_ENOBUFS;
+  const uint32_t ipp = u ? 17u : 50u;                                            // udpencap.c:241
   // the header: 5 .. 15 dwords, all loaded before anything is stored
   const uint32_t nw = skip / 4;
   uint32_t w[15];
@@ -135,7 +145,7 @@ ESPGPU_HD inline int esp_encap_rule(const espgpu_encsa *e, const espgpu_eshape &
     } else if (!(f & ESPGPU_ENC_ECN_NOCARE)) {
       otos &= ~3u;                                                               // ECN_FORBIDDEN
     }
-    uint8_t *oip = pkt - hlen - oh;
+    uint8_t *oip = pkt - hlen - oh - u;
     if (af6) {                                                                   // :969-984
       mem_st32(oip, 0x60u | (otos >> 4) | (otos & 0xfu) << 12);
       mem_st32(oip + 4, enc_be16(total - 40) | 50u << 16 | (uint32_t)e->ttl << 24);   // :742, xform_esp.c:842
@@ -151,33 +161,41 @@ ESPGPU_HD inline int esp_encap_rule(const espgpu_encsa *e, const espgpu_eshape &
       uint32_t h[15];
 #pragma unroll
       for (uint32_t k = 5; k < 15; ++k) h[k] = 0;
-      h[0] = 0x45u | otos << 8 | enc_be16(total) << 16;                          // :727
+      h[0] = 0x45u | otos << 8 | enc_be16(total + u) << 16;                      // :727, udpencap.c:240
       h[1] = enc_be16(id) | (setdf ? 0x40u << 16 : 0u);
-      h[2] = (uint32_t)e->ttl | 50u << 8;
+      h[2] = (uint32_t)e->ttl | ipp << 8;
       h[3] = src[0];
       h[4] = dst[0];
       h[2] |= enc_cksum(h) << 16;                                                // ip_output.c:780-782
 #pragma unroll
       for (uint32_t k = 0; k < 5; ++k) mem_st32(oip + 4 * k, h[k]);
+      if (u) {                                                                   // udpencap.c:233-237
+        mem_st32(oip + 20, dst[1]);
+        mem_st32(oip + 24, enc_be16(total + u - 20));                            // uh_ulen; uh_sum = 0
+      }
     }
   } else {
-    // 6. transport: the header moves down by hlen, fixed on the way
+    // 6. transport: the header moves down by hlen (+ 8), fixed on the way
     if (in6) {
       nxt = (w[1] >> 16) & 0xffu;
       w[1] = (w[1] & 0xff000000u) | 50u << 16 | enc_be16(total - 40);            // :742, xform_esp.c:842
     } else {
       nxt = (w[2] >> 8) & 0xffu;
-      w[0] = (w0 & 0xffffu) | enc_be16(total) << 16;                             // :727
-      w[2] = (w[2] & 0xffu) | 50u << 8;
+      w[0] = (w0 & 0xffffu) | enc_be16(total + u) << 16;                         // :727, udpencap.c:240
+      w[2] = (w[2] & 0xffu) | ipp << 8;
       w[2] |= enc_cksum(w) << 16;
     }
 #pragma unroll
     for (uint32_t k = 0; k < 15; ++k)
-      if (k < nw) mem_st32(pkt - hlen + 4 * k, w[k]);
+      if (k < nw) mem_st32(pkt - hlen - u + 4 * k, w[k]);
+    if (u) {                                                                     // udpencap.c:233-237
+      mem_st32(pkt - hlen - 8 + skip, dst[1]);
+      mem_st32(pkt - hlen - 4 + skip, enc_be16(total + u - skip));               // uh_ulen; uh_sum = 0
+    }
   }
   // 7.
-  o->front = hlen + oh;
-  o->total = total;
+  o->front = hlen + oh + u;
+  o->total = total + u;
   o->reclen = reclen;
   o->frame = rlen | nxt << 16;
   return 0;

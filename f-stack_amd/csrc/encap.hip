@@ -103,6 +103,8 @@ __global__ __launch_bounds__(256) void snt_kernel(SntArgs a) {
     sa = a.desc[i].sa;
     accepted = a.status[i] == 0 && sa < a.nenc;
     booked = a.opkt[i].len;
+    // key_sa_recordxfer runs before the UDP header exists (ipsec_output.c:770, :808)
+    if (accepted && (a.enc[sa].flags & ESPGPU_ENC_NATT)) booked -= 8;
   }
   // key_sa_recordxfer (ipsec_output.c:770).  Each wave first sums its leading
   // SA (the SA of its first accepted lane); when that covers every accepted

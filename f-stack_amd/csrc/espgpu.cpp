@@ -1034,6 +1034,11 @@ int espgpu_set_tuning(espgpu_ctx *c, const char *key, int value) {
     c->deadline_ms = (uint32_t)value;
     return 0;
   }
+  if (!strcmp(key, "natt_lanes")) {
+    if (value != 0 && value != 8 && value != 16 && value != 32) return ESPGPU_EINVAL;
+    c->natt_lanes = (uint32_t)value;
+    return 0;
+  }
   if (!strcmp(key, "gcm_burst")) {
     if (value < 0) return ESPGPU_EINVAL;
     c->gcm_burst = (uint32_t)value;

@@ -1,13 +1,14 @@
 // espgpu_batch.cpp — the kernel launches of the host runtime (espgpu_ctx.h):
 // run_batch, the device-resident batch entry points with their single-record
 // counterparts beside them (the rules are classify.h's, decap.h's, encap.h's,
-// frame.h's and replay.h's), and the host-to-host pipeline.
+// frame.h's, natt.h's and replay.h's), and the host-to-host pipeline.
 #include "espgpu_ctx.h"
 
 #include "classify.h"      // (after the HIP runtime's vector types)
 #include "decap.h"
 #include "encap.h"
 #include "frame.h"
+#include "natt.h"
 #include "replay.h"
 
 namespace espgpu {
@@ -392,7 +393,7 @@ int espgpu_sad_build(const espgpu_sad_entry *sas, uint32_t nsas, espgpu_sad_entr
 int espgpu_esp_classify(const espgpu_sad_entry *table, uint32_t nslots, const uint8_t *pkt, uint32_t len,
                         uint32_t off4, uint32_t flags, espgpu_desc *desc) {
   if (!desc) return ESPGPU_EINVAL;
-  if (!table || nslots == 0 || (nslots & (nslots - 1)) || (!pkt && len) || (flags & ~(uint32_t)ESPGPU_CLS_IPCSUM)) {
+  if (!table || nslots == 0 || (nslots & (nslots - 1)) || (!pkt && len) || (flags & ~kClsKnown)) {
     *desc = espgpu_desc{off4, 0, 0xffff, 0, 0};
     return ESPGPU_EINVAL;
   }
@@ -402,7 +403,7 @@ int espgpu_esp_classify(const espgpu_sad_entry *table, uint32_t nslots, const ui
 int espgpu_esp_classify_batch(espgpu_ctx *c, const uint8_t *d_arena, const espgpu_pkt *d_pkt, uint32_t n,
                               const espgpu_sad_entry *d_table, uint32_t nslots, uint32_t flags, espgpu_desc *d_desc,
                               uint8_t *d_cstatus, void *stream) {
-  if (!c || (flags & ~(uint32_t)ESPGPU_CLS_IPCSUM)) return ESPGPU_EINVAL;
+  if (!c || (flags & ~kClsKnown)) return ESPGPU_EINVAL;
   if (n && (!d_arena || !d_pkt || !d_table || !d_desc || !d_cstatus || nslots == 0 || (nslots & (nslots - 1)) ||
             ((uintptr_t)d_arena & 3) || ((uintptr_t)d_table & 15)))
     return ESPGPU_EINVAL;
@@ -446,6 +447,34 @@ int espgpu_esp_decap_batch(espgpu_ctx *c, const uint8_t *d_arena, uint8_t *d_out
   });
 }
 
+// ---- the NAT-T checksum fix (step 5b) -----------------------------------------
+// udp_ipsec_adjust_cksum for one decapsulated packet.  The rule
+// espgpu_esp_natt_cksum_batch applies (natt.h).
+int espgpu_esp_natt_cksum(const espgpu_insa *in, uint8_t *pkt, uint32_t len, uint32_t trailer, uint32_t policy,
+                          uint8_t *out_cflags) {
+  if (out_cflags) *out_cflags = 0;
+  if (!in || !pkt) return ESPGPU_EINVAL;
+  if (!(in->flags & ESPGPU_IN_NATT)) return 0;
+  const uint32_t cf = natt_cksum_rule(pkt, len, trailer & 0xffu, policy, in->natt_cksum);
+  if (out_cflags) *out_cflags = (uint8_t)cf;
+  return 0;
+}
+
+int espgpu_esp_natt_cksum_batch(espgpu_ctx *c, uint8_t *d_out, const espgpu_pkt *d_ipkt, const espgpu_desc *d_desc,
+                                const uint32_t *d_trailer, const uint8_t *d_status, const uint8_t *d_dstatus,
+                                uint32_t n, const espgpu_insa *d_in, uint32_t nin, uint32_t policy, uint8_t *d_cflags,
+                                void *stream) {
+  if (!c) return ESPGPU_EINVAL;
+  if (n && (!d_out || !d_ipkt || !d_desc || !d_trailer || !d_status || !d_dstatus || (nin && !d_in) ||
+            ((uintptr_t)d_out & 3)))
+    return ESPGPU_EINVAL;
+  // no workspace and nothing of the ctx's is touched
+  return run_stage(c, n, 0, nullptr, "NAT-T checksum kernel launch failed", [&] {
+    return launch_esp_natt_cksum(d_out, d_ipkt, d_desc, d_trailer, d_status, d_dstatus, n, d_in, nin, policy,
+                                 c->natt_lanes, d_cflags, stream);
+  });
+}
+
 // ---- outbound encapsulation ---------------------------------------------------
 // ipsec4/6_perform_request, ipsec_encap and the header work of esp_output and
 // ipsec_process_done for one packet.  The rule espgpu_esp_encap_batch applies
@@ -471,6 +500,8 @@ int espgpu_esp_encap(const espgpu_encsa *e, const espgpu_eshape *s, uint8_t *pkt
 int espgpu_esp_sent(espgpu_encsa *e, uint8_t status, uint32_t len) {
   if (!e) return ESPGPU_EINVAL;
   if (status == 0) {
+    // a NAT-T SA: key_sa_recordxfer runs before the UDP header exists (ipsec_output.c:770, :808)
+    if ((e->flags & ESPGPU_ENC_NATT) && len >= 8) len -= 8;
     e->bytes += len;                                               // key.c:8429-8445
     e->packets += 1;
   }

@@ -207,6 +207,7 @@ struct espgpu_ctx {
   int xfer_small = 1;            // small batches: staging region moved by the xfer kernel (else hipMemcpyAsync)
   int stage_fused = 1;           // small single-session GCM batches stage their own records (one launch)
   uint32_t gcm_burst = GCM_BURST_DEFAULT;   // small GCM batches of <= this many records: burst kernel
+  uint32_t natt_lanes = 0;       // set_tuning "natt_lanes": lanes per packet of the NAT-T recompute kernel (0: natt.h's)
   // doorbell burst path (set_tuning "door", espgpu_internal.h DoorCtl): a
   // persistent kernel of door_wg workgroups serves single-session GCM
   // batches of <= gcm_burst records with no launch per batch

@@ -273,6 +273,9 @@ int launch_esp_encap(uint8_t *arena, const espgpu_pkt *pkt, const uint16_t *sa, 
                      const espgpu_outsa *out, uint32_t nenc, const DevSA *sas, uint32_t nsas, uint32_t headroom,
                      uint32_t tailroom, uint32_t id0, espgpu_desc *desc, uint32_t *frame, espgpu_pkt *opkt,
                      uint8_t *estatus, void *stream);
+int launch_esp_natt_cksum(uint8_t *out, const espgpu_pkt *ipkt, const espgpu_desc *desc, const uint32_t *trailer,
+                          const uint8_t *status, const uint8_t *dstatus, uint32_t n, const espgpu_insa *in,
+                          uint32_t nin, uint32_t policy, uint32_t lanes, uint8_t *cflags, void *stream);
 int launch_esp_sent(const espgpu_pkt *opkt, const espgpu_desc *desc, const uint8_t *status, uint32_t n,
                     espgpu_encsa *enc, uint32_t nenc, void *stream);
 #ifdef ESPGPU_BOUNDS

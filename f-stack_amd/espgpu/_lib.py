@@ -115,16 +115,24 @@ class SadEntry(C.Structure):
 
 
 CLS_IPCSUM, ENOENT, ENOTSUP = 0x1, 2, 95
+SAD_NATT = 0x2
+
+
+def CLS_NATT_PORT(port):
+    """ESPGPU_CLS_NATT_PORT: the local UDP encapsulation port in the classification flags."""
+    return (port & 0xffff) << 16
 
 
 class InSA(C.Structure):
-    """struct espgpu_insa: one SA's inbound lifetime counters and ESPGPU_IN_* flags."""
+    """struct espgpu_insa: one SA's inbound lifetime counters and ESPGPU_IN_* flags;
+    pad_ is the header's natt_cksum (the field keeps its name here)."""
     _fields_ = [("bytes", C.c_uint64), ("packets", C.c_uint64), ("flags", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 # the same as a numpy record, for batch.esp_decap's insa tensor
 INSA_DTYPE = np.dtype([("bytes", "<u8"), ("packets", "<u8"), ("flags", "<u4"), ("pad_", "<u4")])
 IN_TRANSPORT, IN_TUNNEL, IN_PAD_RAND, IN_AF6 = 0x1, 0x2, 0x4, 0x8
+IN_NATT, NATT_CSUM_VALID = 0x20, 0x1
 ENODATA, EPFNOSUPPORT = 61, 96
 
 
@@ -140,6 +148,7 @@ ENCSA_DTYPE = np.dtype([("bytes", "<u8"), ("packets", "<u8"), ("flags", "<u4"), 
                         ("src", "u1", (16,)), ("dst", "u1", (16,))])
 ENC_TUNNEL, ENC_AF6, ENC_DF_SET, ENC_DF_COPY = 0x01, 0x02, 0x04, 0x08
 ENC_ECN_ALLOWED, ENC_ECN_NOCARE, ENC_RFC6864 = 0x10, 0x20, 0x40
+ENC_NATT = 0x200
 EMSGSIZE, EAFNOSUPPORT, ENOBUFS = 90, 97, 105
 
 
@@ -228,6 +237,11 @@ def lib():
             L.espgpu_esp_encap_batch.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32,
                                                  C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp]
             L.espgpu_esp_sent_batch.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp]
+        if hasattr(L, "espgpu_esp_natt_cksum_batch"):   # (absent from older builds used in A/B runs)
+            L.espgpu_esp_natt_cksum.argtypes = [C.POINTER(InSA), vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.POINTER(C.c_uint8)]
+            L.espgpu_esp_natt_cksum_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32,
+                                                      C.c_uint32, vp, vp]
         L.espgpu_last_kernel_ms.argtypes = [vp]
         L.espgpu_last_kernel_ms.restype = C.c_float
         L.espgpu_set_tuning.argtypes = [vp, C.c_char_p, C.c_int]

@@ -170,7 +170,8 @@ def esp_classify(driver, arena, pkt, n, table, desc, cstatus, flags=0, stream=No
     result of sad_build.  desc receives one descriptor per packet, for the
     rest of the inbound sequence, and cstatus 0 / EINVAL / ENOTSUP / ENOENT,
     for replay_merge at its end; a refused packet's descriptor has len 0 and
-    sa 0xffff.  flags: L.CLS_IPCSUM."""
+    sa 0xffff.  flags: L.CLS_IPCSUM, L.CLS_NATT_PORT(port) to take ESP in UDP
+    to that port."""
     for t in (arena, pkt, table, desc, cstatus):
         assert t.is_cuda and t.is_contiguous()
     assert pkt.numel() >= n * PKT_DTYPE.itemsize and desc.numel() * desc.element_size() >= n * 16
@@ -208,6 +209,31 @@ def esp_decap(driver, arena, out, pkt, desc, trailer, status, n, insa, ipkt, dst
         status.data_ptr(), n, insa.data_ptr(), nin, ipkt.data_ptr(), dstatus.data_ptr(), _stream_ptr(stream))
     if rc:
         raise RuntimeError("espgpu_esp_decap_batch: %s (%d)" % (driver.last_error(), rc))
+
+
+def esp_natt_cksum(driver, out, ipkt, desc, trailer, status, dstatus, n, insa, policy=0, cflags=None, stream=None):
+    """The NAT-T checksum fix after esp_decap (espgpu_esp_natt_cksum_batch):
+    out, ipkt, desc, trailer, status and dstatus as esp_decap took and left
+    them (before the final replay_merge, or after it with status given for
+    both), insa its INSA_DTYPE tensor, whose pad_ field holds natt->cksum for
+    the SAs with L.IN_NATT.  policy 0 adjusts the TCP / UDP checksum of every
+    decapsulated transport packet of such an SA by that value, nonzero
+    recomputes it over the segment.  cflags, if given, receives one byte per
+    packet: L.NATT_CSUM_VALID where the stack is to take the TCP checksum as
+    verified, else 0."""
+    for t in (out, ipkt, desc, trailer, status, dstatus, insa) + ((cflags,) if cflags is not None else ()):
+        assert t.is_cuda and t.is_contiguous()
+    assert trailer.element_size() == 4 and trailer.numel() >= n
+    assert ipkt.numel() * ipkt.element_size() >= n * PKT_DTYPE.itemsize
+    assert desc.numel() * desc.element_size() >= n * 16 and status.numel() >= n and dstatus.numel() >= n
+    assert cflags is None or (cflags.element_size() == 1 and cflags.numel() >= n)
+    nin = insa.numel() * insa.element_size() // INSA_DTYPE.itemsize
+    rc = driver.lib.espgpu_esp_natt_cksum_batch(
+        driver.ctx, out.data_ptr(), ipkt.data_ptr(), desc.data_ptr(), trailer.data_ptr(), status.data_ptr(),
+        dstatus.data_ptr(), n, insa.data_ptr(), nin, policy, cflags.data_ptr() if cflags is not None else None,
+        _stream_ptr(stream))
+    if rc:
+        raise RuntimeError("espgpu_esp_natt_cksum_batch: %s (%d)" % (driver.last_error(), rc))
 
 
 ENCSA_DTYPE = L.ENCSA_DTYPE

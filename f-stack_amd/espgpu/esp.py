@@ -588,6 +588,255 @@ def esp_sent_host(encsa, status, length):
     return L.lib().espgpu_esp_sent(C.byref(encsa), status, length)
 
 
+# ---- NAT-T: ESP in UDP (netipsec/udpencap.c) ------------------------------------
+IPPROTO_TCP, IPPROTO_UDP = 6, 17
+
+
+def _reduce16(total):
+    """REDUCE16 with ADDCARRY (amd64/in_cksum.c:61-73) on a 64-bit sum."""
+    l = sum((total >> (16 * k)) & 0xffff for k in range(4))             # q_util.s[0..3]
+    total = (l & 0xffff) + (l >> 16)                                    # l_util.s[0] + l_util.s[1]
+    if total > 65535:                                                   # ADDCARRY
+        total -= 65535
+    return total
+
+
+def in_addword(a, b):
+    """in_addword (in_cksum.c:174-181) on two 16-bit values as the host
+    loaded them."""
+    total = a + b
+    if total > 65535:                                                   # ADDCARRY
+        total -= 65535
+    return total
+
+
+def in_pseudo(a, b, c):
+    """in_pseudo (in_cksum.c:183-193): a and b are the addresses as 32-bit
+    loads of their network-order bytes on the little-endian host, c what
+    htons() gave."""
+    return _reduce16(a + b + c)
+
+
+def _in_cksumdata(buf):
+    """in_cksumdata (in_cksum.c:93-172) for a 4-byte aligned buffer on the
+    little-endian host: the dwords, the tail under in_masks, REDUCE32."""
+    buf = bytes(buf)
+    nw = len(buf) // 4
+    total = sum(struct.unpack("<%dI" % nw, buf[:4 * nw]))
+    if len(buf) % 4:                                                    # :168-169
+        total += int.from_bytes(buf[4 * nw:], "little")
+    return sum((total >> (16 * k)) & 0xffff for k in range(4))          # REDUCE32
+
+
+def in_cksum_skip(m, length, skip):
+    """in_cksum_skip (in_cksum.c:195-234) on one contiguous mbuf whose byte
+    `skip` is 4-byte aligned."""
+    return ~_reduce16(_in_cksumdata(bytes(m)[skip:length])) & 0xffff
+
+
+def in_delayed_cksum(m, udp, csum_data):
+    """in_delayed_cksum (ip_output.c:1059-1091) on a bytearray packet: udp is
+    csum_flags & CSUM_UDP, csum_data the field's offset in the transport
+    header.  The 16-bit values are the little-endian host's loads."""
+    offset = (m[0] & 0xf) << 2                                          # :1066
+    if udp:
+        cklen = struct.unpack(">H", m[offset + 4:offset + 6])[0]        # ntohs(uh->uh_ulen), :1076
+        csum = in_cksum_skip(m, cklen + offset, offset)                 # :1078
+        if csum == 0:
+            csum = 0xffff                                               # :1079-1080
+    else:
+        cklen = struct.unpack(">H", m[2:4])[0]                          # ntohs(ip->ip_len), :1082
+        csum = in_cksum_skip(m, cklen, offset)                          # :1083
+    offset += csum_data                                                 # :1085
+    m[offset:offset + 2] = struct.pack("<H", csum)                      # :1087-1090
+
+
+def udp_ipsec_adjust_cksum(packet, natt_cksum, proto, skip, policy):
+    """udp_ipsec_adjust_cksum (udpencap.c:245-293) on a decapsulated packet's
+    bytes: natt_cksum is sav->natt->cksum as the host holds it, proto 6 or 17,
+    skip the IP header's length, policy V_natt_cksum_policy.  Returns (packet
+    bytes, valid): valid stands for csum_flags |= CSUM_DATA_VALID |
+    CSUM_PSEUDO_HDR with csum_data 0xffff (:274-276).  What the reference
+    leaves to its callers is decided here as the engine decides it: a packet
+    too short to hold the field, and under the recompute policy a UDP length
+    outside [8, len - skip] or a TCP packet whose ip_len is not the packet's
+    length (the reference would sum past the mbuf), come back unchanged."""
+    m = bytearray(packet)
+    assert proto in (IPPROTO_TCP, IPPROTO_UDP)                          # :253
+    off = 6 if proto == IPPROTO_UDP else 16                             # :256-259
+    if len(m) - skip < off + 2:
+        return bytes(m), False
+    at = skip + off
+    if policy == 0:                                                     # auto, :261
+        if natt_cksum != 0:
+            cksum = struct.unpack("<H", m[at:at + 2])[0]                # m_copydata, :264
+            if proto == IPPROTO_UDP and cksum == 0:                     # :267-268
+                return bytes(m), False
+            cksum = in_addword(cksum, natt_cksum)                       # :269
+        else:
+            if proto == IPPROTO_TCP:                                    # :272-278
+                return bytes(m), True
+            cksum = 0                                                   # :279
+        m[at:at + 2] = struct.pack("<H", cksum)                         # m_copyback, :281
+        return bytes(m), False
+    if proto == IPPROTO_UDP:
+        ulen = struct.unpack(">H", m[skip + 4:skip + 6])[0]
+        if ulen < 8 or ulen > len(m) - skip:
+            return bytes(m), False
+    elif struct.unpack(">H", m[2:4])[0] != len(m):
+        return bytes(m), False
+    src, dst = struct.unpack("<II", m[12:20])
+    htons = lambda x: struct.unpack("<H", struct.pack(">H", x & 0xffff))[0]   # noqa: E731
+    cksum = in_pseudo(src, dst, htons(len(m) - skip + proto))           # :284-285
+    m[at:at + 2] = struct.pack("<H", cksum)                             # :286
+    in_delayed_cksum(m, proto == IPPROTO_UDP, off)                      # :287-290
+    return bytes(m), False
+
+
+def udp_input_encap_checks(pkt, hlen, port):
+    """udp_input's way to the UF_ESPINUDP socket for an IPv4 non-fragment
+    datagram already trimmed to ip_len (udp_usrreq.c:335-339, :460-475,
+    :489-520), as far as the device path follows it: the datagram must be for
+    `port`, its length fields sane (:468-472, the trim :474), and its checksum
+    field 0: a nonzero one would be verified over the whole datagram, which
+    stays the host's.  Returns (status, trimmed packet)."""
+    if len(pkt) - hlen < 8:                                             # udps_hdrops: the host's error
+        return L.ENOTSUP, pkt
+    sport, dport, ulen, uh_sum = struct.unpack(">HHHH", pkt[hlen:hlen + 8])
+    if dport != port:                                                   # another socket's
+        return L.ENOTSUP, pkt
+    if ulen != len(pkt) - hlen:                                         # :468
+        if ulen > len(pkt) - hlen or ulen < 8:                          # :469-471
+            return L.EINVAL, pkt
+        pkt = pkt[:hlen + ulen]                                         # m_adj, :474
+    if uh_sum != 0:                                                     # :489-520
+        return L.ENOTSUP, pkt
+    return 0, pkt
+
+
+def udp_ipsec_input(sadb, pkt, hlen):
+    """udp_ipsec_input (udpencap.c:115-210) for AF_INET: pkt is the datagram
+    as udp_input_encap_checks left it, sadb maps an SPI to (sa, proto, af, dst
+    bytes, salt, natt) with natt None or (sport, dport).  Returns (status,
+    sav): 0 with the SA's tuple for a packet IPsec consumes, ENOTSUP where the
+    function returns 0 (the socket gets the datagram: keepalive, IKE)."""
+    off = hlen + 8
+    if len(pkt) < off + 8:                                              # :131-132
+        return L.ENOTSUP, None
+    spi = struct.unpack(">I", pkt[off:off + 4])[0]                      # :134
+    if spi == 0:                                                        # :135-136
+        return L.ENOTSUP, None
+    if (len(pkt) - off) % 4:                                            # xform_esp.c:279, before the lookup as the engine's
+        return L.EINVAL, None
+    sav = sadb.get(spi)                                                 # key_allocsa, :166
+    if sav is None:
+        return L.ENOENT, None
+    sa, proto, saf, sdst, salt = sav[:5]
+    natt = sav[5] if len(sav) > 5 else None
+    if proto != IPPROTO_ESP or saf != 4 or bytes(sdst)[:4] != pkt[16:20]:      # key.c:1110-1118
+        return L.ENOENT, None
+    sport, dport = struct.unpack(">HH", pkt[hlen:hlen + 4])
+    if natt is None or natt[0] != sport or natt[1] != dport:            # :173-181
+        return L.ENOENT, None
+    return 0, sav
+
+
+def ipsec_input_classify_natt(sadb, pkt, off4=0, ipcsum=False, port=0):
+    """ipsec_input_classify with the UDP-encapsulation socket on `port`
+    (0: none, and the result is ipsec_input_classify's except for the last
+    point).  sadb's tuples may carry a sixth member, natt: None or (sport,
+    dport).  An IPv4 non-fragment with ip_p 17 goes through
+    udp_input_encap_checks and udp_ipsec_input; accepted, the descriptor is
+    the ESP record behind the UDP header.  One deliberate difference from the
+    reference: a plain ip_p 50 packet whose SA has natt is ENOTSUP, the host
+    stack's (ipsec_common_input would take it)."""
+    raw = bytes(pkt)
+    plain = {spi: tuple(v[:5]) for spi, v in sadb.items()}
+    st, d = ipsec_input_classify(plain, raw, off4, ipcsum)
+    if st == 0:
+        spi = struct.unpack(">I", raw[(d[0] - off4) * 4:(d[0] - off4) * 4 + 4])[0]
+        if len(sadb[spi]) > 5 and sadb[spi][5] is not None:
+            return L.ENOTSUP, (off4, 0, 0xffff, 0, 0)
+        return st, d
+    if not port or st != L.ENOTSUP or len(raw) < 20 or raw[0] >> 4 != 4 or raw[9] != IPPROTO_UDP:
+        return st, d
+    ip_off = struct.unpack(">H", raw[6:8])[0]
+    if ip_off & (IP_MF | IP_OFFMASK):
+        return st, d
+    hlen = (raw[0] & 0xf) << 2
+    raw = raw[:struct.unpack(">H", raw[2:4])[0]]                        # the trim, ip_input.c:555-561
+    st, raw = udp_input_encap_checks(raw, hlen, port)
+    if st == 0:
+        st, sav = udp_ipsec_input(sadb, raw, hlen)
+    if st:
+        return st, (off4, 0, 0xffff, 0, 0)
+    return 0, (off4 + (hlen + 8) // 4, len(raw) - hlen - 8, sav[0], 0, sav[4])
+
+
+def esp_input_decap_natt(mode, prand, ivlen, alen, packet_bytes, skip):
+    """esp_input_decap for a packet that came through udp_ipsec_input: `skip`
+    covers the IP header and the 8 UDP bytes.  The UDP header is stripped and
+    ip_p set first (udpencap.c:149, :196), then esp_input runs with the IP
+    header's length as its skip (:208).  Returns esp_input_decap's triple."""
+    m = bytes(packet_bytes)
+    if skip % 4 or not 28 <= skip <= 68:
+        return L.EINVAL, None, 0
+    hl = skip - 8
+    m = m[:hl] + m[skip:]                                               # m_striphdr(m, hlen, sizeof(*udp)), :196
+    m = m[:9] + bytes([IPPROTO_ESP]) + m[10:]                           # :149
+    return esp_input_decap(mode, False, prand, ivlen, alen, m, hl)
+
+
+def udp_ipsec_output(wire, sport, dport):
+    """udp_ipsec_output (udpencap.c:212-243) on the wire packet of
+    ipsec_output_encap (a list with None for the bytes left to framing and
+    encryption), AF_INET: the UDP header behind the IP header, ip_len and
+    ip_p; then ip_output's checksum over the finished header
+    (ip_output.c:780-782)."""
+    hlen = (wire[0] & 0xf) << 2                                         # :226
+    total = len(wire) + 8
+    udp = struct.pack(">HHHH", sport, dport, total - hlen, 0)           # :233-237
+    wire = wire[:hlen] + list(udp) + wire[hlen:]                        # m_makespace, :227
+    wire[2:4] = list(struct.pack(">H", total))                          # :240
+    wire[9] = IPPROTO_UDP                                               # :241
+    wire[10:12] = [0, 0]
+    wire[10:12] = list(struct.pack(">H", in_cksum(bytes(wire[:hlen]))))
+    return wire
+
+
+def ipsec_output_encap_natt(tunnel, saf6, src, dst, ttl, dfbit, ecn, rfc6864, ivlen, blks, alen, packet, headroom,
+                            tailroom, ip_id, sport, dport):
+    """ipsec_output_encap for an SA with natt: ipsec_process_done calls
+    udp_ipsec_output on the finished ESP packet (ipsec_output.c:804-813).  An
+    AF_INET6 SA is EAFNOSUPPORT (udpencap.c:222-223; decided first here, with
+    the SA's other checks).  A wire packet of more than 65535 bytes is
+    EMSGSIZE (the reference lets ip_len wrap, :240), and the 8 bytes count
+    against the headroom (ENOBUFS, :227-231).  Returns ipsec_output_encap's
+    four, front and wire with the UDP header."""
+    if saf6:
+        return L.EAFNOSUPPORT, 0, None, 0
+    st, front, wire, nxt = ipsec_output_encap(tunnel, saf6, src, dst, ttl, dfbit, ecn, rfc6864, ivlen, blks, alen,
+                                              packet, headroom, tailroom, ip_id)
+    if st:
+        return st, front, wire, nxt
+    if len(wire) + 8 > IP_MAXPACKET:
+        return L.EMSGSIZE, 0, None, 0
+    if front + 8 > headroom:
+        return L.ENOBUFS, 0, None, 0
+    return 0, front + 8, udp_ipsec_output(wire, sport, dport), nxt
+
+
+def esp_natt_cksum_host(insa, buf, at, length, trailer, policy):
+    """espgpu_esp_natt_cksum, the engine's host rule, on a bytearray that
+    holds the decapsulated packet at `at` and an L.InSA: returns (status,
+    cflags)."""
+    import ctypes as C
+    raw = (C.c_uint8 * (len(buf) - at)).from_buffer(buf, at)
+    cf = C.c_uint8(0xdd)
+    rc = L.lib().espgpu_esp_natt_cksum(C.byref(insa), C.cast(raw, C.c_void_p), length, trailer, policy, C.byref(cf))
+    return rc, cf.value
+
+
 def trailer_word(plain_payload):
     """The 32-bit word the kernels' fused trailer check produces for a
     decrypted payload (espgpu_decrypt_batch_trailer, include/espgpu.h):

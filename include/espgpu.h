@@ -46,6 +46,8 @@ extern "C" {
 #endif
 
 #define ESPGPU_ABI_VERSION 6
+#define ESPGPU_HAS_NATT 1   /* the NAT-T block below is built; the ABI version stays: new symbols and
+                             flag bits that were refused before, no layout change */
 
 /* ---- constants, numerically identical to freebsd/opencrypto/cryptodev.h ---- */
 #define ESPGPU_CSP_MODE_CIPHER      2        /* cryptodev.h:362: ESP without auth */
@@ -371,6 +373,10 @@ int  espgpu_decrypt_host(espgpu_ctx *ctx, const uint8_t *h_arena, uint64_t arena
  *                                  input_cb: trailer verdict, strip, header fix,
  *                                  SA lifetime counters (the decapsulation block
  *                                  below; reads d_status as 4 left it)
+ *  5b. espgpu_esp_natt_cksum_batch udp_ipsec_adjust_cksum for the transport
+ *                                  packets of NAT-T SAs (the NAT-T block below;
+ *                                  reads d_status and 5's d_dstatus); only for
+ *                                  a caller with such SAs
  *   6. espgpu_replay_merge         with 5's: (d_status, d_dstatus, n).
  * espgpu_replay_update / _update64 are the same update on the host, one
  * record per call. */
@@ -561,15 +567,24 @@ struct espgpu_sad_entry {      /* 32 B: one slot of the SPI table; spi == 0: fre
 	uint8_t  proto;            /* 50 (ESP) or 51 (AH): saidx.proto                     */
 	uint8_t  af;               /* 4 or 6                                               */
 	uint32_t salt;             /* as espgpu_desc.salt; copied into the descriptor      */
-	uint32_t flags;            /* reserved, 0                                          */
-	uint8_t  dst[16];          /* saidx.dst: 4 bytes + 12 zeros for af 4               */
+	uint32_t flags;            /* 0 or ESPGPU_SAD_NATT                                 */
+	uint8_t  dst[16];          /* saidx.dst: 4 bytes + 12 zeros for af 4; with
+	                              ESPGPU_SAD_NATT natt->sport in dst[4..5] and
+	                              natt->dport in dst[6..7], network order           */
 };
 #define ESPGPU_CLS_IPCSUM 0x1  /* verify the IPv4 header checksum (ip_input.c:518-530) */
+#define ESPGPU_SAD_NATT   0x2  /* sav->natt != NULL (keydb.h:94-103): proto 50, af 4 only */
+/* Bits 16-31 of the classification flags: the local UDP encapsulation port in
+ * host order (the socket with UF_ESPINUDP, udp_usrreq.c:335); 0: off. */
+#define ESPGPU_CLS_NATT_PORT(p) ((uint32_t)((p) & 0xffffu) << 16)
 /* Host: zero table[nslots] and insert sas[nsas] in order.  ESPGPU_EINVAL
  * (table contents then unspecified) unless nslots is a power of two with
  * nslots >= 2 * nsas (so a free slot ends every probe), and for an entry with
  * spi 0, an SPI seen before (key.c:1106-1109), proto not 50 or 51, af not 4
- * or 6, an af 4 entry whose dst[4..15] is not zero, or flags != 0. */
+ * or 6, flags other than 0 or ESPGPU_SAD_NATT, ESPGPU_SAD_NATT on an entry
+ * that is not proto 50 and af 4 (udpencap.c:155-163: IPv4 outer only), an af
+ * 4 entry without the flag whose dst[4..15] is not zero, or one with it whose
+ * dst[8..15] is not zero. */
 int  espgpu_sad_build(const struct espgpu_sad_entry *sas, uint32_t nsas,
                       struct espgpu_sad_entry *table, uint32_t nslots);
 /* Host: classify one packet of `len` bytes at `pkt`; `off4` is where it lies
@@ -577,7 +592,7 @@ int  espgpu_sad_build(const struct espgpu_sad_entry *sas, uint32_t nsas,
  * skip / 4, record length, entry.sa, 0, entry.salt}; any other status fills
  * {off4, 0, 0xffff, 0, 0}, which the replay check, the decrypt kernels and the
  * window update all pass over.  Nothing is read outside [pkt, pkt + len), and
- * of the packet nothing beyond the IP header and the SPI.  The checks, in
+ * of the packet nothing beyond the IP header, a UDP header and the SPI.  The checks, in
  * order; the first that fires decides:
  *   1. len < 20, version nibble neither 4 nor 6                      EINVAL
  *   2. IPv4: hlen = ip_hl * 4 < 20, or hlen > len                    EINVAL
@@ -585,10 +600,26 @@ int  espgpu_sad_build(const struct espgpu_sad_entry *sas, uint32_t nsas,
  *      ip_len < hlen, or ip_len > len                                EINVAL
  *        (bytes past ip_len are ignored: the trim, ip_input.c:555-561)
  *      a fragment, ip_off & (IP_MF | IP_OFFMASK)                     ENOTSUP
- *      ip_p != 50 (AH, IPComp, UDP-encapsulated ESP, non-IPsec)      ENOTSUP
+ *      ip_p == 17 with a port in flags: 2a below decides
+ *      ip_p != 50 (AH, IPComp, non-IPsec; UDP without a port set)    ENOTSUP
  *      ip_len - hlen < 8 (ipsec_input.c:141)                         EINVAL
  *      ip_len & 3 (xform_esp.c:279)                                  EINVAL
  *      skip = hlen, record length = ip_len - hlen
+ *  2a. ESP in UDP (RFC 3948), only with ESPGPU_CLS_NATT_PORT(port) in flags
+ *      (port 0: off, and every UDP packet is ENOTSUP as above); udp_input up
+ *      to the UF_ESPINUDP socket (udp_usrreq.c:335-339, :468-474) and
+ *      udp_ipsec_input (udpencap.c:115-210):
+ *      ip_len - hlen < 8, or uh_dport != port (an ordinary datagram)  ENOTSUP
+ *      uh_ulen < 8, or uh_ulen > ip_len - hlen (:468-472)            EINVAL
+ *        (bytes past uh_ulen are ignored: the trim, :474; ulen = uh_ulen)
+ *      uh_sum != 0 (udp_input would verify it over the whole
+ *        datagram, :489-520; RFC 3948 senders send 0)                ENOTSUP
+ *      ulen - 8 < 8 (the keepalive, udpencap.c:131-132)              ENOTSUP
+ *      the SPI dword is 0 (the non-ESP marker: IKE, :135)            ENOTSUP
+ *      (ulen - 8) & 3 (xform_esp.c:279)                              EINVAL
+ *      skip = hlen + 8, record length = ulen - 8; after the lookup of 4:
+ *      the entry lacks ESPGPU_SAD_NATT, or uh_sport / uh_dport are not
+ *        its dst[4..5] / dst[6..7] (udpencap.c:173-181)              ENOENT
  *   3. IPv6: len < 40                                                EINVAL
  *      payload length 0 (jumbogram)                                  ENOTSUP
  *      40 + plen > len                                               EINVAL
@@ -599,8 +630,13 @@ int  espgpu_sad_build(const struct espgpu_sad_entry *sas, uint32_t nsas,
  *   4. the SPI (big-endian dword at skip) is 0, no slot holds it, or the
  *      slot's proto != 50, its af is not the packet's, or its dst is
  *      not the packet's destination (4 or 16 bytes)                  ENOENT
- * Fragments, AH and everything else answered ENOTSUP are the host stack's
- * packets.  Not re-checked: the per-transform lengths (the decrypt kernels'
+ *      a plain ip_p 50 packet whose entry has ESPGPU_SAD_NATT        ENOTSUP
+ *        (a deliberate difference: ipsec_common_input would take it, but the
+ *        later steps tell a UDP-encapsulated packet by its SA alone, so the
+ *        host stack decides)
+ * Fragments, AH, UDP-encapsulated ESP with a nonzero UDP checksum, NAT-T
+ * keepalives, IKE and everything else answered ENOTSUP are the host stack's
+ * packets; IPv6 NAT-T does not exist in the reference either.  Not re-checked: the per-transform lengths (the decrypt kernels'
  * EINVAL), whether session `sa` exists (theirs too), loopback and other
  * address filters (ip_input's; the caller's).  A null or unusable table
  * (nslots not a power of two) is EINVAL. */
@@ -627,21 +663,25 @@ int  espgpu_esp_classify_batch(espgpu_ctx *ctx, const uint8_t *d_arena,
  * record, its status and its trailer word to the packet the stack takes next.
  * One SA's inbound state as those functions read and advance it; the entry at
  * index `sa` belongs to the session with that id.  Left to the caller or the
- * host stack: the NAT-T checksum adjustment (classification sends NAT-T to
- * the host already), the hhooks / enc(4), ipsec_if_input, ip_input of the
- * inner packet and the SPD check. */
+ * host stack: the hhooks / enc(4), ipsec_if_input, ip_input of the inner
+ * packet and the SPD check.  The NAT-T checksum adjustment is step 5b, the
+ * NAT-T block below. */
 #define ESPGPU_IN_TRANSPORT 0x1   /* saidx.mode == IPSEC_MODE_TRANSPORT                      */
 #define ESPGPU_IN_TUNNEL    0x2   /* IPSEC_MODE_TUNNEL; neither bit: IPSEC_MODE_ANY; both: unusable */
 #define ESPGPU_IN_PAD_RAND  0x4   /* SADB_X_EXT_PRAND: ESPGPU_TR_BADPAD is ignored (:613)    */
 #define ESPGPU_IN_AF6       0x8   /* saidx.dst is AF_INET6 (esp_input_cb picks the callback
                                      by the SA's family, :638-648); clear: AF_INET           */
+#define ESPGPU_IN_NATT      0x20  /* sav->natt != NULL: the packet came UDP-encapsulated
+                                     (the NAT-T block below); AF_INET only                   */
 #define ESPGPU_ENODATA      61    /* next header IPPROTO_NONE: RFC 4303 2.6 dummy, dropped   */
 #define ESPGPU_EPFNOSUPPORT 96    /* ipsec4_common_input_cb: "cannot handle inner ip proto"  */
 struct espgpu_insa {              /* 24 B, indexed by session id, lives in device memory     */
 	uint64_t bytes;               /* lft_c_bytes                                             */
 	uint64_t packets;             /* lft_c_allocations                                       */
 	uint32_t flags;               /* ESPGPU_IN_*                                             */
-	uint32_t pad_;
+	uint32_t natt_cksum;          /* low 16 bits: sav->natt->cksum, the raw value that is
+	                                 added to the checksum field's two bytes as they lie in
+	                                 memory; read by espgpu_esp_natt_cksum only              */
 };
 /* Host: decapsulate one packet of SA `in`.  `pkt` points at the outer IP
  * header (`skip` bytes), the decrypted record lies at pkt + skip and is rlen
@@ -652,7 +692,10 @@ struct espgpu_insa {              /* 24 B, indexed by session id, lives in devic
  * decides, and a refused packet has nothing written, books nothing and gets
  * *out_off = *out_len = 0:
  *   1. flags with unknown bits or both mode bits                     EINVAL
- *      skip & 3; skip not in 20..60 (AF_INET) or not 40 (AF6)        EINVAL
+ *      ESPGPU_IN_NATT with ESPGPU_IN_AF6                             EINVAL
+ *      skip & 3; skip not in 20..60 (AF_INET), 28..68 (AF_INET with
+ *        ESPGPU_IN_NATT: the IP header and the 8 UDP bytes), or not
+ *        40 (AF6)                                                    EINVAL
  *      plen < 2 (also ivlen not 0, 8 or 16)                          EINVAL
  *      the trailer word without ESPGPU_TR_VALID                      EINVAL
  *      ESPGPU_TR_BADLEN (xform_esp.c:601, esps_badilen)              EINVAL
@@ -681,6 +724,12 @@ struct espgpu_insa {              /* 24 B, indexed by session id, lives in devic
  *      overlap whenever hlen < skip).  The result is {hlen, skip + q} and the
  *      SA books skip + q bytes.  [pkt, pkt + hlen), the padding, the trailer
  *      and the ICV stay as they are (m_adj only shortens, :633).
+ *      ESPGPU_IN_NATT: the IP header is the first skip - 8 bytes and moves
+ *      forward by hlen + 8, over the UDP header too (the m_striphdr of
+ *      udpencap.c:196 and that of xform_esp.c:588); ip_hl * 4 != skip - 8 is
+ *      EINVAL, ip_len = skip - 8 + q, and the result is {hlen + 8, skip - 8 +
+ *      q} with as many bytes booked.  A tunnel result is {skip + hlen, q} as
+ *      ever.
  *   6. accepted: in->bytes += booked, in->packets += 1 (key.c:8429-8445).
  * *out_off is relative to pkt, *out_len the new m_pkthdr.len.  Null pointers
  * are EINVAL. */
@@ -735,8 +784,9 @@ int  espgpu_esp_decap_batch(espgpu_ctx *ctx, const uint8_t *d_arena, uint8_t *d_
  * to the caller or the host stack: the SPD lookup that picks the SA (d_sa),
  * the hhooks / enc(4), random ip_id (ip_do_randomid needs a CSPRNG: the ids
  * here are a counter's), link-local SA addresses (the scope embedding of
- * ipsec_output.c:975-981), NAT-T, fragmentation of the result and
- * ip_output of it. */
+ * ipsec_output.c:975-981), fragmentation of the result and ip_output of it.
+ * udp_ipsec_output's header (ESPGPU_ENC_NATT) is built here, in its final wire
+ * form: it depends on lengths only, so nothing moves after the encrypt. */
 #define ESPGPU_ENC_TUNNEL      0x01  /* sp->req[idx]->saidx.mode == IPSEC_MODE_TUNNEL          */
 #define ESPGPU_ENC_AF6         0x02  /* saidx.dst is AF_INET6; clear: AF_INET                  */
 #define ESPGPU_ENC_DF_SET      0x04  /* V_ip4_ipsec_dfbit 1: DF set in an outer IPv4 header    */
@@ -746,6 +796,9 @@ int  espgpu_esp_decap_batch(espgpu_ctx *ctx, const uint8_t *d_arena, uint8_t *d_
 #define ESPGPU_ENC_ECN_NOCARE  0x20  /* -1 (ECN_NOCARE); neither bit: ECN_FORBIDDEN, the
                                         default; both: unusable                                */
 #define ESPGPU_ENC_RFC6864     0x40  /* V_ip_rfc6864: ip_id 0 when DF is set (ip_id.c:252)     */
+#define ESPGPU_ENC_NATT        0x200 /* sav->natt != NULL: udp_ipsec_output's header (the NAT-T
+                                        block below); natt->sport in dst[4..5], natt->dport in
+                                        dst[6..7], network order; AF_INET only                 */
 #define ESPGPU_EMSGSIZE     90    /* the result would exceed IP_MAXPACKET (xform_esp.c:747)  */
 #define ESPGPU_EAFNOSUPPORT 97    /* the packet is neither IPv4 nor IPv6 (ipsec_output.c:933) */
 struct espgpu_encsa {             /* 56 B, indexed by session id, lives in device memory     */
@@ -765,6 +818,8 @@ struct espgpu_encsa {             /* 56 B, indexed by session id, lives in devic
  * do).  The checks in order; the first that fires decides, and a refused
  * packet has nothing written and zeros in the four results:
  *   1. flags with unknown bits, both DF bits or both ECN bits          EINVAL
+ *      ESPGPU_ENC_NATT with ESPGPU_ENC_AF6 (udpencap.c:222-223)        EAFNOSUPPORT
+ *      ESPGPU_ENC_NATT and src[4..15] or dst[8..15] not zero           EINVAL
  *      an AF6 SA whose src or dst is unspecified (:961-964)            EINVAL
  *      an AF6 SA whose src or dst is in fe80::/10 (the host's)         ENOTSUP
  *   2. len < 20 (nothing is read)                                      EINVAL
@@ -789,6 +844,9 @@ struct espgpu_encsa {             /* 56 B, indexed by session id, lives in devic
  *      total > 65535 (xform_esp.c:747)                                 EMSGSIZE
  *      hlen + oh > headroom, or padding + alen > tailroom (where
  *      m_makespace and m_pad would fail, :772-780, :810-818)           ENOBUFS
+ *      ESPGPU_ENC_NATT: total + 8 > 65535 is EMSGSIZE (a deliberate
+ *      difference: the reference lets ip_len wrap, udpencap.c:240), checked
+ *      behind the first; the headroom needed is hlen + oh + 8 (:227-231).
  *   5. tunnel: first the inner header is fixed: IPv4 ip_len = len, ip_sum
  *      zeroed and recomputed over ip_hl * 4 bytes (ipsec_output.c:230-232);
  *      IPv6 ip6_plen = len - 40 (:533).  Then the outer header goes to pkt -
@@ -814,6 +872,14 @@ struct espgpu_encsa {             /* 56 B, indexed by session id, lives in devic
  *      behind the outer header (at pkt - hlen) or behind the moved header (at
  *      pkt - hlen + skip), 4-byte aligned with pkt.  *out_frame = rlen | next
  *      header << 16.
+ *   8. ESPGPU_ENC_NATT (udp_ipsec_output, udpencap.c:212-243): the IP header
+ *      of 5 or 6 (the outer one, or the moved one) lies 8 bytes further down,
+ *      and between it and the ESP header stand uh_sport = dst[4..5], uh_dport
+ *      = dst[6..7], uh_ulen = total + 8 - the IP header's length, uh_sum = 0.
+ *      The IP header has ip_p = 17, ip_len = total + 8 and ip_sum over the
+ *      finished header.  The frame word's next header (4 / 41 / the old
+ *      ip_p), the record's position and *out_reclen are as without the flag;
+ *      *out_front = hlen + oh + 8 and *out_total = total + 8.
  * Only the header bytes named above are written: not the payload, the ESP
  * header, the IV, the padding, the trailer or the ICV field, which are
  * framing's and encryption's.  The counters are espgpu_esp_sent's.  Null
@@ -824,8 +890,9 @@ int  espgpu_esp_encap(const struct espgpu_encsa *e, const struct espgpu_eshape *
                       uint32_t *out_frame);
 /* Host: key_sa_recordxfer of ipsec_process_done (ipsec_output.c:770) for one
  * packet that went through with status `status`: 0 books `len` bytes (the wire
- * packet's total) and one packet into *e, anything else nothing.  Returns 0,
- * or EINVAL for a null e. */
+ * packet's total; len - 8 for an ESPGPU_ENC_NATT SA: the reference books
+ * before the UDP header exists, ipsec_output.c:770, :808) and one packet into
+ * *e, anything else nothing.  Returns 0, or EINVAL for a null e. */
 int  espgpu_esp_sent(struct espgpu_encsa *e, uint8_t status, uint32_t len);
 /* The same rule for n packets of a device-resident arena.  d_pkt[i] is the
  * cleartext packet, d_sa[i] the SA the caller's SPD lookup chose for it,
@@ -854,8 +921,8 @@ int  espgpu_esp_encap_batch(espgpu_ctx *ctx, uint8_t *d_arena, const struct espg
                             uint32_t *d_frame, struct espgpu_pkt *d_opkt, uint8_t *d_estatus,
                             void *stream);
 /* espgpu_esp_sent for a batch, after the merges: a record with d_status[i] ==
- * 0 and d_desc[i].sa < nenc books d_opkt[i].len bytes and one packet into
- * d_enc[sa].  A step of its own because a record that framing refuses
+ * 0 and d_desc[i].sa < nenc books d_opkt[i].len bytes (8 fewer for an
+ * ESPGPU_ENC_NATT SA) and one packet into d_enc[sa].  A step of its own because a record that framing refuses
  * (WRAPCHECK) never reaches ipsec_process_done in the reference either.  The
  * sums are order-free: summed per wave, and per workgroup where one SA has all
  * of it, before the 64-bit adds, as espgpu_esp_decap_batch's.  Asynchronous on
@@ -863,6 +930,66 @@ int  espgpu_esp_encap_batch(espgpu_ctx *ctx, uint8_t *d_arena, const struct espg
 int  espgpu_esp_sent_batch(espgpu_ctx *ctx, const struct espgpu_pkt *d_opkt,
                            const struct espgpu_desc *d_desc, const uint8_t *d_status, uint32_t n,
                            struct espgpu_encsa *d_enc, uint32_t nenc, void *stream);
+
+/* ---- NAT-T: ESP in UDP (RFC 3948; freebsd/netipsec/udpencap.c:115-293, called
+ *      from netinet/udp_usrreq.c:335-339, netipsec/ipsec_output.c:804-813 and
+ *      ipsec_input.c:318-326; struct secnatt, keydb.h:94-103) ----
+ * The rule parts live in the blocks above: ESPGPU_SAD_NATT and
+ * ESPGPU_CLS_NATT_PORT (classification, 2a), ESPGPU_IN_NATT (decapsulation)
+ * and ESPGPU_ENC_NATT (encapsulation, 8; espgpu_esp_sent).  NAT-T is IPv4-outer
+ * only, as the reference's (udpencap.c:155-163, :222-223).  Still the host
+ * stack's: inbound datagrams with a nonzero UDP checksum, keepalives, IKE on
+ * the same port, and IPv6 NAT-T, which the reference lacks.
+ *
+ * Step 5b of the inbound sequence, after espgpu_esp_decap_batch:
+ * udp_ipsec_adjust_cksum (udpencap.c:245-293) on the decapsulated packet, the
+ * transport-mode TCP / UDP checksum fix for addresses a NAT rewrote.
+ * `policy` is net.inet.ipsec.natt_cksum_policy: 0 auto, nonzero recompute.
+ * A packet of `len` bytes at `pkt` with next header nxt = trailer & 0xff takes
+ * part if the SA has ESPGPU_IN_NATT and nxt is 6 or 17 (`prot` at
+ * ipsec_input.c:318; never a tunnel result).  The transport header starts at
+ * ip_hl * 4 and the checksum field is at +16 (TCP) or +6 (UDP).  Left alone:
+ * a packet that is not IPv4 with 20 <= ip_hl * 4 <= len <= 65535, or too
+ * short to hold the field.
+ *   auto (:261-281), delta = the low 16 bits of in->natt_cksum:
+ *     delta != 0: a zero UDP checksum stays (:267-268); otherwise field =
+ *       in_addword(field, delta), both as 16-bit values in memory order.
+ *     delta == 0: the UDP field becomes 0 (:279).  TCP is untouched and
+ *       *out_cflags = ESPGPU_NATT_CSUM_VALID: what the reference says with
+ *       CSUM_DATA_VALID | CSUM_PSEUDO_HDR and csum_data 0xffff (:272-278).
+ *   recompute (:282-292 with in_delayed_cksum, ip_output.c:1059-1091): field =
+ *     ~(in_pseudo(ip_src, ip_dst, htons(len - ip_hl * 4 + nxt)) + the segment
+ *     with the field as zero), the segment being ip_len - ip_hl * 4 bytes for
+ *     TCP and uh_ulen bytes for UDP, an odd last byte as the low byte of a
+ *     word (in_masks), and for UDP a result of 0 stored as 0xffff.  The sums
+ *     fold as the reference's REDUCE16 / ADDCARRY do: 0 only for a sum of 0.
+ *     Left alone (deliberately: the reference would sum past the mbuf, or a
+ *     span the pseudo-header does not describe): a UDP packet with uh_ulen < 8
+ *     or uh_ulen > len - ip_hl * 4, a TCP packet with ip_len != len.
+ * Nothing but the field's two bytes is written, and nothing outside [pkt, pkt
+ * + len) is read.  *out_cflags (optional) is 0 in every other case.  Returns
+ * 0, or EINVAL for a null in or pkt. */
+#define ESPGPU_NATT_CSUM_VALID 0x1
+int  espgpu_esp_natt_cksum(const struct espgpu_insa *in, uint8_t *pkt, uint32_t len,
+                           uint32_t trailer, uint32_t policy, uint8_t *out_cflags);
+/* The same rule for a device-resident batch.  Packet i takes part if
+ * d_status[i] == 0, d_dstatus[i] == 0, d_desc[i].sa < nin, that SA has
+ * ESPGPU_IN_NATT and d_trailer[i] & 0xff is 6 or 17; it is the d_ipkt[i].len
+ * bytes at d_out + d_ipkt[i].off4 * 4, as espgpu_esp_decap_batch left them.
+ * d_cflags may be null; otherwise d_cflags[i] is written for every i < n.
+ * Policy auto runs one lane per packet.  Recompute reads every byte of every
+ * taking-part segment with a group of lanes per packet (16 unless set_tuning
+ * "natt_lanes" says 8 or 32), aligned dword loads that each hold at least one
+ * byte of the segment, and one dword store per packet: the field's, which on
+ * the device may rewrite up to two bytes behind a TCP packet of 18 or 19
+ * segment bytes with their own values (they are the record's padding).  d_out
+ * is 4-byte aligned (EINVAL otherwise).  Asynchronous on the caller's stream,
+ * no workspace, no host round trip; n == 0 is a no-op that returns 0. */
+int  espgpu_esp_natt_cksum_batch(espgpu_ctx *ctx, uint8_t *d_out, const struct espgpu_pkt *d_ipkt,
+                                 const struct espgpu_desc *d_desc, const uint32_t *d_trailer,
+                                 const uint8_t *d_status, const uint8_t *d_dstatus, uint32_t n,
+                                 const struct espgpu_insa *d_in, uint32_t nin, uint32_t policy,
+                                 uint8_t *d_cflags, void *stream);
 
 /* Device time of the last timed batch's crypto kernels (ms, from HIP events
  * on the batch stream).  Process-path batches of <= 128 KiB (a burst on its
@@ -879,6 +1006,8 @@ float espgpu_last_kernel_ms(espgpu_ctx *ctx);
  *               requests not yet moved into a slot count against it);
  *   "xfer"      small batches' staging region moved by the xfer kernel (1,
  *               default) or by hipMemcpyAsync (0);
+ *   "natt_lanes" lanes per packet of espgpu_esp_natt_cksum_batch's recompute
+ *               kernel: 0 (default: 16), 8, 16 or 32; others EINVAL;
  *   "gcm_burst" GCM batches of up to this many records (default 4096) that
  *               run the small-batch design, out of place or encrypt, use the
  *               burst kernel (a 32-lane CTR pass and an 8-lane GHASH in one
