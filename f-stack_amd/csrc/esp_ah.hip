@@ -266,11 +266,11 @@ __global__ __launch_bounds__(kDigWG) void digest_kernel(DigestParams p) {
       if (have) di = esp_at_ld(CHK_ORDER, p.order, ch.start + lane);
     }
     bool mine = false, valid = false, verify = false, esn = false, ok = false;
-    uint32_t off = 0, len = 0, sa = 0, esnh = 0, icvo = 0, mlen = 0;
+    uint32_t off4 = 0, len = 0, sa = 0, esnh = 0, icvo = 0, mlen = 0;
     int hq = 0;                                   // narrow: 1 SHA-1, 2 SHA2-256; wide: 1 SHA2-384, 2 SHA2-512
     if (have) {
       const uint4 dv = esp_desc_ld16(p.desc, di);
-      off = dv.x * 4;
+      off4 = dv.x;
       len = dv.y & 0xffffu;
       sa = dv.y >> 16;
       esnh = dv.z;
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(kDigWG) void digest_kernel(DigestParams p) {
           hq = (s->aalg == ESPGPU_CRYPTO_SHA2_256_HMAC || s->aalg == ESPGPU_CRYPTO_SHA2_512_HMAC) ? 2 : 1;
       }
     }
-    const uint8_t *rec = p.arena + off;
+    const uint8_t *rec = p.arena + (size_t)off4 * 4;
     // the batch path hashes the ICV field as zeros; the driver path the
     // record as it stands
     const uint32_t hlo = p.op == 2 ? 0u : icvo, hhi = p.op == 2 ? 0u : icvo + mlen;
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(kDigWG) void digest_kernel(DigestParams p) {
           ok = diff == 0;
         } else if (act) {
           for (uint32_t k = 0; k < mlen / 4; ++k)
-            esp_st4(p.icv_out + off + icvo + 4 * k, bswap32(dg[k]));
+            esp_st4(p.icv_out + (size_t)off4 * 4 + icvo + 4 * k, bswap32(dg[k]));
         }
       }
     } else {
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(kDigWG) void digest_kernel(DigestParams p) {
           ok = diff == 0;
         } else if (act) {
           for (uint32_t k = 0; k < mlen / 4; ++k)
-            esp_st4(p.icv_out + off + icvo + 4 * k, bswap32(dg[k]));
+            esp_st4(p.icv_out + (size_t)off4 * 4 + icvo + 4 * k, bswap32(dg[k]));
         }
       }
     }

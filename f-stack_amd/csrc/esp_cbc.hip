@@ -710,8 +710,10 @@ __device__ __forceinline__ void fill_pair(uint8_t *lds, uint32_t base, const uin
 }
 
 // The verified decrypt of a wave unit (MODE 2 in place, MODE 3 to p.out):
-// run = this lane's record passed verification; (sa, off, plen, di, salt) its
-// session, offset, payload length, descriptor index and salt.  All of the
+// run = this lane's record passed verification; (sa, off4, plen, di, salt) its
+// session, offset in 4-byte units (the descriptor's own, widened to 64 bits
+// only where a pointer is formed: the arena is up to 16 GiB), payload length,
+// descriptor index and salt.  All of the
 // wave's blocks of one session as one flat list: records to decrypt (one
 // session at a time, so the round keys stay wave-uniform in SGPRs) are
 // concatenated; every lane takes one block per pass, last pass first.
@@ -720,7 +722,7 @@ __device__ __forceinline__ void fill_pair(uint8_t *lds, uint32_t base, const uin
 // in-place decryption is safe without holding records in registers.
 template <int MODE>
 __device__ __forceinline__ void verified_decrypt(const EtaParams &p, const uint8_t *lds, uint32_t slot, int lane,
-                                                 bool run, uint32_t sa, uint32_t off, uint32_t plen, uint32_t di,
+                                                 bool run, uint32_t sa, uint32_t off4, uint32_t plen, uint32_t di,
                                                  uint32_t salt) {
   uint64_t todo = __ballot(run);
   while (todo) {
@@ -777,7 +779,7 @@ __device__ __forceinline__ void verified_decrypt(const EtaParams &p, const uint8
         }
         fk[k] = f;
         ik[k] = (uint32_t)f - sj;
-        rok[k] = __shfl(off, j);
+        rok[k] = __shfl(off4, j);
         // (each __shfl is a ds_bpermute on the LDS pipe the AES lookups
         // bound: only what the session kind uses, wave-uniform conditions)
         rplk[k] = (ctr || null || p.trailer) ? __shfl(plen, j) : 0u;
@@ -790,7 +792,7 @@ __device__ __forceinline__ void verified_decrypt(const EtaParams &p, const uint8
       for (int k = 0; k < U; ++k) {
         v[k] = pv[k] = make_uint4(0, 0, 0, 0);
         if (fk[k] >= 0 && !(eopts() & 0x80000)) {             // knob: no decrypt-pass loads
-          const uint8_t *rec = p.arena + rok[k];
+          const uint8_t *rec = p.arena + (size_t)rok[k] * 4;
           if (null) {
             v[k] = ld16(rec + 8 + 16 * ik[k]);                                     // P_i = C_i
           } else if (ctr) {
@@ -812,7 +814,8 @@ __device__ __forceinline__ void verified_decrypt(const EtaParams &p, const uint8
 #pragma unroll
       for (int k = 0; k < U; ++k) {
         if (fk[k] >= 0 && !(eopts() & 0x80000)) {             // knob: no decrypt-pass stores
-          uint8_t *dst = (MODE == 2 ? p.arena : p.out) + rok[k];   // MODE 3: p.out (may be p.arena)
+          // MODE 3: p.out (may be p.arena)
+          uint8_t *dst = (MODE == 2 ? p.arena : p.out) + (size_t)rok[k] * 4;
           const uint32_t i = ik[k], rpl = rplk[k];
           const int rem = (int)rpl - 16 * (int)i;
           const uint4 pt = xor4(v[k], pv[k]);
@@ -885,13 +888,13 @@ __global__ __launch_bounds__(WG, 1) void eta_kernel(EtaParams p) {
     }
     // ---- lane = record: descriptor, HMAC (verify or compute) ----
     bool valid = false, ok = false;
-    uint32_t off = 0, len = 0, sa = 0, plen = 0, hl = 24, salt = 0, esnh = 0;
+    uint32_t off4 = 0, len = 0, sa = 0, plen = 0, hl = 24, salt = 0, esnh = 0;
     int hq = 0;                                  // MODE 2 narrow: 1 SHA-1 / 2 SHA2-256 record to hash
     bool hq_esn = false;
     uint32_t hq_mlen = 0;
     if (have) {
       const uint4 dv = *reinterpret_cast<const uint4 *>(p.desc + di);
-      off = dv.x * 4;
+      off4 = dv.x;
       len = dv.y & 0xffffu;
       sa = dv.y >> 16;
       esnh = dv.z;
@@ -928,7 +931,7 @@ __global__ __launch_bounds__(WG, 1) void eta_kernel(EtaParams p) {
           hq_mlen = mlen;
         } else if (valid && (MODE == 2 || MODE == 3)) {
           uint32_t dg[16];
-          const uint8_t *rec = p.arena + off;
+          const uint8_t *rec = p.arena + (size_t)off4 * 4;
           if (CKS == CK_NARROW) {              // SHA-1 / SHA2-256 only: no SHA-512 code, fewer VGPRs
             if (s->aalg == ESPGPU_CRYPTO_SHA2_256_HMAC)
               hmac_t<HS_SHA256>(rec, hl + plen, (s->flags & ESPGPU_CSP_F_ESN) != 0, esnh, kp(s->ipad),
@@ -954,7 +957,7 @@ __global__ __launch_bounds__(WG, 1) void eta_kernel(EtaParams p) {
         if (!__any(hq == hs)) continue;           // wave-uniform
         const bool act = hq == hs;
         const DevSA *s = p.sas + (act ? sa : 0u);
-        const uint8_t *rec = p.arena + off;
+        const uint8_t *rec = p.arena + (size_t)off4 * 4;
         uint32_t dg[16];
         if (hs == 2)
           hmac_quad<HS_SHA256, 2>(act, rec, hl + plen, hq_esn, esnh, kp(s->ipad), kp(s->opad), dg);
@@ -991,17 +994,17 @@ __global__ __launch_bounds__(WG, 1) void eta_kernel(EtaParams p) {
         if (CKS == CK_CBCMAC) {                   // the chain and, for SHA-1 / SHA2-256, the ICV
           const bool esn = (s->flags & ESPGPU_CSP_F_ESN) != 0;
           if (s->aalg == ESPGPU_CRYPTO_SHA1_HMAC)
-            cbc_mac_quad<HS_SHA1>(mine, p.arena + off, plen, kp(s->rk), nr, lds, slot, esn, esnh, kp(s->ipad),
-                                  kp(s->opad), s->mlen);
+            cbc_mac_quad<HS_SHA1>(mine, p.arena + (size_t)off4 * 4, plen, kp(s->rk), nr, lds, slot, esn, esnh,
+                                  kp(s->ipad), kp(s->opad), s->mlen);
           else if (s->aalg == ESPGPU_CRYPTO_SHA2_256_HMAC)
-            cbc_mac_quad<HS_SHA256>(mine, p.arena + off, plen, kp(s->rk), nr, lds, slot, esn, esnh,
+            cbc_mac_quad<HS_SHA256>(mine, p.arena + (size_t)off4 * 4, plen, kp(s->rk), nr, lds, slot, esn, esnh,
                                     kp(s->ipad), kp(s->opad), s->mlen);
           else                                    // no auth, or SHA2-384/512 (the wide MAC pass)
-            cbc_enc_quad<1>(mine, p.arena + off, plen / 16, kp(s->rk), nr, lds, slot);
+            cbc_enc_quad<1>(mine, p.arena + (size_t)off4 * 4, plen / 16, kp(s->rk), nr, lds, slot);
           continue;
         }
         if (CKS != CK_CTR || !mine) continue;
-        uint8_t *rec = p.arena + off;
+        uint8_t *rec = p.arena + (size_t)off4 * 4;
         const uint32_t iv0 = *reinterpret_cast<const uint32_t *>(rec + 8);
         const uint32_t iv1 = *reinterpret_cast<const uint32_t *>(rec + 12);
         const uint32_t nb = (plen + 15) / 16;
@@ -1036,7 +1039,7 @@ __global__ __launch_bounds__(WG, 1) void eta_kernel(EtaParams p) {
         if (!__any(hq1 == hs)) continue;          // wave-uniform
         const bool act = hq1 == hs;
         const DevSA *s = p.sas + (act ? sa : 0u);
-        uint8_t *rec = p.arena + off;
+        uint8_t *rec = p.arena + (size_t)off4 * 4;
         uint32_t dg[16];
         if (hs == 2)
           hmac_quad<HS_SHA256, 2>(act, rec, hl + plen, act && (s->flags & ESPGPU_CSP_F_ESN) != 0, esnh,
@@ -1050,7 +1053,7 @@ __global__ __launch_bounds__(WG, 1) void eta_kernel(EtaParams p) {
       }
       if (CKS != CK_NARROW && have && valid && hq1 == 0 && p.sas[sa].aalg != 0) {   // CSP_MODE_CIPHER: no ICV
         const DevSA *s = p.sas + sa;
-        uint8_t *rec = p.arena + off;
+        uint8_t *rec = p.arena + (size_t)off4 * 4;
         uint32_t dg[16];
         hmac_any((int)s->aalg, rec, hl + plen, (s->flags & ESPGPU_CSP_F_ESN) != 0, esnh, kp(s->ipad),
                  kp(s->opad), dg);
@@ -1065,7 +1068,7 @@ __global__ __launch_bounds__(WG, 1) void eta_kernel(EtaParams p) {
     // decrypting a record's last block writes the others'
     if (have && p.trailer && !(valid && ok)) p.trailer[di] = 0;
 
-    verified_decrypt<MODE>(p, lds, slot, lane, have && valid && ok, sa, off, plen, di, salt);
+    verified_decrypt<MODE>(p, lds, slot, lane, have && valid && ok, sa, off4, plen, di, salt);
   }
   // Every wave leaves the loop after drawing one ticket past the end, so once
   // all have retired no ticket is drawn again: reset for the next launch.

@@ -272,6 +272,9 @@ int  espgpu_get_stats(espgpu_ctx *ctx, struct espgpu_stats *st);
 /* ---- device-resident batch path ----
  * d_arena: device buffer holding the records (padded by >= 16 bytes at its
  * end); d_desc[n]; d_status[n] receives one errno byte per record.
+ * The arena (and d_out) may be up to 16 GiB: off4 counts 4-byte units and its
+ * whole 32-bit range is valid, here and in espgpu_pkt; every kernel and every
+ * batch stage forms a record's address as d_arena + (size_t)off4 * 4.
  * decrypt: plaintext goes to d_out at the same offsets (d_out may equal
  * d_arena: verify-first in place; an EBADMSG record ends byte-identical to
  * its ciphertext: AES-GCM in one pass that XORs the keystream back over a

@@ -206,7 +206,7 @@ TRL_FILL = 0x5A5A5A5A
 MODES = ["sign", "inplace", "outofplace"]
 
 
-def check(drv, lay, sids, mode, grouped=True):
+def check(drv, lay, sids, mode, grouped=True, place=None):
     """Run lay on the GPU and compare with the reference; nothing is left out:
       * sign (encrypt_batch): 0 for every well-formed record, EINVAL for the
         others; the whole arena equals `signed`, byte for byte;
@@ -218,7 +218,20 @@ def check(drv, lay, sids, mode, grouped=True):
         layouts names a DIGEST session or none at all; a record without a
         session is answered EINVAL with the trailer word 0, as for every
         other kind of session.)
-    sids: the device's session id per entry of lay.sas."""
+    sids: the device's session id per entry of lay.sas.
+    place (high_offset_helpers.Placed): the layout lies at place.base of a
+    large arena, every off4 relocated; the same comparisons run on that window
+    of the arena and of `out`, and place.finish() then requires every byte
+    outside the window untouched."""
+    if place is None:
+        return _check(drv, lay, sids, mode, grouped, None)
+    try:
+        return _check(drv, lay, sids, mode, grouped, place)
+    finally:
+        place.finish()
+
+
+def _check(drv, lay, sids, mode, grouped, place):
     import torch
     from espgpu.batch import decrypt_batch, encrypt_batch
     signed, bad, vst = reference(lay)
@@ -230,7 +243,11 @@ def check(drv, lay, sids, mode, grouped=True):
     d["sa"] = [sids[s] for s in lay.descs["sa"]]
     d["sa"][lay.orphan] = 0xFFFF
     n = lay.n
-    arena = torch.from_numpy(np.array(src)).cuda()
+    if place is None:
+        arena = win = torch.from_numpy(np.array(src)).cuda()
+    else:
+        d = place.relocate(d)
+        arena, win = place.load(src)               # win: the layout's bytes inside arena
     descs = torch.from_numpy(np.ascontiguousarray(d).view(np.uint8).copy()).cuda()
     st = torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda")
     trl = torch.from_numpy(np.full(n, TRL_FILL, dtype=np.uint32).view(np.int32)).cuda()
@@ -240,7 +257,7 @@ def check(drv, lay, sids, mode, grouped=True):
     elif mode == "inplace":
         decrypt_batch(drv, arena, descs, n, st, out=None, grouped=grouped, trailer=trl)
     else:
-        out = torch.full_like(arena, OUT_FILL)
+        out, owin = (torch.full_like(arena, OUT_FILL),) * 2 if place is None else place.out(OUT_FILL)
         decrypt_batch(drv, arena, descs, n, st, out=out, grouped=grouped, trailer=trl)
     torch.cuda.synchronize()
     got = st.cpu().numpy()
@@ -248,11 +265,11 @@ def check(drv, lay, sids, mode, grouped=True):
     assert not len(wrong), "%s: %d statuses differ (lengths %s), first: got %d, expected %d at %s" % (
         mode, len(wrong), sorted({int(lay.L[i]) for i in wrong})[:24], got[wrong[0]], want_st[wrong[0]],
         lay.where(wrong[0]))
-    diff = arena.cpu().numpy() != want_arena
+    diff = win.cpu().numpy() != want_arena
     assert not diff.any(), "%s: %d bytes of the arena differ, first at %s" % (
         mode, int(diff.sum()), lay.where_byte(int(np.argmax(diff))))
     if out is not None:
-        diff = out.cpu().numpy() != OUT_FILL
+        diff = owin.cpu().numpy() != OUT_FILL
         assert not diff.any(), "out was written at " + lay.where_byte(int(np.argmax(diff)))
     if not sign:
         gt = trl.cpu().numpy().view(np.uint32)

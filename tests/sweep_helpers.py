@@ -221,7 +221,7 @@ OUT_FILL = 0xA5
 TRL_FILL = 0xEEEEEEEE
 
 
-def check(drv, b, sids, mode, grouped=True):
+def check(drv, b, sids, mode, grouped=True, place=None):
     """Run b on the GPU (mode: "outofplace", "inplace" or "encrypt") and
     compare with the oracle:
       * statuses equal for every record;
@@ -235,7 +235,20 @@ def check(drv, b, sids, mode, grouped=True):
         promises an untouched failed record only in place, not that an
         out-of-place verify-first decrypt writes nothing;
       * decrypt: trailer words (prefilled) equal esp.trailer_word of the
-        oracle's plaintext for verified records, 0 for every other."""
+        oracle's plaintext for verified records, 0 for every other.
+    place (high_offset_helpers.Placed): the layout lies at place.base of a
+    large arena, every off4 relocated; the same comparisons run on that window
+    of the arena and of `out`, and place.finish() then requires every byte
+    outside the window untouched."""
+    if place is None:
+        return _check(drv, b, sids, mode, grouped, None)
+    try:
+        return _check(drv, b, sids, mode, grouped, place)
+    finally:
+        place.finish()
+
+
+def _check(drv, b, sids, mode, grouped, place):
     import torch
     from espgpu.batch import decrypt_batch, encrypt_batch
     enc = mode == "encrypt"
@@ -245,7 +258,11 @@ def check(drv, b, sids, mode, grouped=True):
     d["sa"] = [sids[s] for s in b.descs["sa"]]
     d["sa"][b.orphan] = 0xFFFF
     n = b.n
-    arena = torch.from_numpy(np.array(src)).cuda()
+    if place is None:
+        arena = win = torch.from_numpy(np.array(src)).cuda()
+    else:
+        d = place.relocate(d)
+        arena, win = place.load(src)               # win: the layout's bytes inside arena
     descs = torch.from_numpy(np.ascontiguousarray(d).view(np.uint8).copy()).cuda()
     st = torch.full((n,), 0xEE, dtype=torch.uint8, device="cuda")
     trl = torch.from_numpy(np.full(n, TRL_FILL, dtype=np.uint32).view(np.int32)).cuda()
@@ -255,21 +272,21 @@ def check(drv, b, sids, mode, grouped=True):
     elif mode == "inplace":
         decrypt_batch(drv, arena, descs, n, st, out=None, grouped=grouped, trailer=trl)
     else:
-        out = torch.full_like(arena, OUT_FILL)
+        out, owin = (torch.full_like(arena, OUT_FILL),) * 2 if place is None else place.out(OUT_FILL)
         decrypt_batch(drv, arena, descs, n, st, out=out, grouped=grouped, trailer=trl)
     torch.cuda.synchronize()
     got = st.cpu().numpy()
     wrong = np.nonzero(got != ref_st)[0]
     assert not len(wrong), "%d statuses differ (payload lengths %s), first: got %d, the oracle %d at %s" % (
         len(wrong), sorted({b.payload(i) for i in wrong})[:24], got[wrong[0]], ref_st[wrong[0]], b.where(wrong[0]))
-    res = arena.cpu().numpy()
+    res = win.cpu().numpy()
     if mode == "outofplace":
         assert (res == src).all(), "out of place: the arena changed at " + b.where_byte(int(np.argmax(res != src)))
         want = np.full_like(src, OUT_FILL)
         okm = _payload_mask(b.descs, ref_st == 0, len(src), b.sas)
         want[okm] = ref[okm]
         care = ~_payload_mask(b.descs, ref_st == O.EBADMSG, len(src), b.sas)
-        diff = (out.cpu().numpy() != want) & care
+        diff = (owin.cpu().numpy() != want) & care
         assert not diff.any(), "out differs at " + b.where_byte(int(np.argmax(diff)))
     else:
         diff = res != ref

@@ -479,6 +479,58 @@ def test_cksum_batch_arguments(env, sum_batch):
 
 
 # ---- (d) the whole loop ------------------------------------------------------------------
+def end_to_end_packets(policy):
+    """The loop's sessions and cleartext packets, seeded by policy (no GPU):
+    -> (sas, tun, natt, delta, outsa, enc, sa, pkts, protos, head, tail, arena, rec)."""
+    from espgpu import _lib as L
+    from espgpu.batch import ENCSA_DTYPE, OUTSA_DTYPE
+    rng = np.random.default_rng(1306 + policy)
+    sas = [GcmSA(rng), EtaSA(rng), GcmSA(rng, 32), EtaSA(rng, sha256=True), GcmSA(rng), EtaSA(rng)]
+    tun = [False, False, True, True, False, True]
+    natt = [True, True, True, True, False, False]                   # two plain SAs beside them
+    delta = [0x1234, 0, 0x00ff, 0, 0x7777, 0]
+    nsa = len(sas)
+    outsa = np.zeros(nsa, dtype=OUTSA_DTYPE)
+    enc = np.zeros(nsa, dtype=ENCSA_DTYPE)
+    for k, s in enumerate(sas):
+        outsa[k] = (100 * k, 5000 * k, s.spi, int.from_bytes(s.salt, "little"), L.OUT_PAD_SEQ, 0)
+        enc["flags"][k] = (L.ENC_TUNNEL if tun[k] else 0) | (L.ENC_NATT if natt[k] else 0) | L.ENC_DF_COPY
+        enc["ttl"][k] = 40 + k
+        for f in ("src", "dst"):
+            enc[f][k, :4] = np.frombuffer(EH.addr(rng, False), dtype=np.uint8)
+        if natt[k]:
+            enc["dst"][k, 4:8] = np.frombuffer(struct.pack(">HH", 3000 + k, PORT), dtype=np.uint8)
+    enc["bytes"], enc["packets"] = 1000, 10
+    n = 200
+    sa = rng.integers(0, nsa, n)
+    pkts, protos = [], []
+    for k in sa:
+        proto = int(rng.choice([6, 17, 1]))
+        body = bytearray(rng.integers(0, 256, int(rng.integers(0, 300)), dtype=np.uint8).tobytes())
+        if proto == 17 and len(body) >= 8:
+            body[4:6] = struct.pack(">H", len(body))
+        if tun[k] and rng.random() < 0.3:
+            pkts.append(CH.ipv6(EH.addr(rng, True), body, nxt=proto))
+        else:
+            dst = EH.addr(rng, False) if tun[k] else enc["dst"][k, :4].tobytes()
+            ihl = int(rng.integers(5, 16))
+            pkts.append(CH.ipv4(dst, body, ihl=ihl, proto=proto,
+                                opts=rng.integers(0, 256, ihl * 4 - 20, dtype=np.uint8).tobytes()))
+        protos.append(proto)
+    head, tail = 72, 49
+    arena, rec = EH.layout(rng, pkts, head, tail)
+    return sas, tun, natt, delta, outsa, enc, sa, pkts, protos, head, tail, arena, rec
+
+
+def _back(place, a):
+    """A structured array the device wrote, its off4 as at base 0."""
+    if place is None:
+        return a
+    a = a.copy()
+    a["off4"] = place.back(a["off4"])
+    return a
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("policy", [0, 1], ids=["auto", "recompute"])
 def test_outbound_then_inbound_end_to_end_with_natt(policy):
@@ -487,54 +539,37 @@ def test_outbound_then_inbound_end_to_end_with_natt(policy):
     merges -> decap -> natt_cksum, on GCM and CBC+HMAC SAs in transport and
     tunnel mode: the results are the packets that went in, with the checksum
     esp.udp_ipsec_adjust_cksum predicts for the transport ones."""
+    end_to_end(policy)
+
+
+def end_to_end(policy, placed=None):
+    """The loop with its arena at base 0 of a tensor of its own, or (placed: a
+    function from the arena and the packet list to a
+    high_offset_helpers.Placed) at a high offset of a large one: only the
+    cleartext packet list is relocated by the test; every later offset is the
+    device's own and is compared after subtracting base / 4."""
     torch = _torch()
     from espgpu import _lib as L
     from espgpu import esp as E
-    from espgpu.batch import (ENCSA_DTYPE, INSA_DTYPE, OUTSA_DTYPE, PKT_DTYPE, REPLAY_DTYPE, SAD_DTYPE,
+    from espgpu.batch import (ENCSA_DTYPE, INSA_DTYPE, PKT_DTYPE, REPLAY_DTYPE, SAD_DTYPE,
                               decrypt_batch, encrypt_batch, esp_classify, esp_decap, esp_encap, esp_frame,
                               esp_natt_cksum, esp_sent, replay_check, replay_merge, replay_update, sad_build)
     from espgpu.opencrypto import GpuCryptoDriver
-    rng = np.random.default_rng(1306 + policy)
-    sas = [GcmSA(rng), EtaSA(rng), GcmSA(rng, 32), EtaSA(rng, sha256=True), GcmSA(rng), EtaSA(rng)]
-    tun = [False, False, True, True, False, True]
-    natt = [True, True, True, True, False, False]                   # two plain SAs beside them
-    delta = [0x1234, 0, 0x00ff, 0, 0x7777, 0]
-    nsa = len(sas)
+    sas, tun, natt, delta, outsa, enc, sa, pkts, protos, head, tail, arena, rec = end_to_end_packets(policy)
+    nsa, n = len(sas), len(pkts)
     drv = GpuCryptoDriver(max_sessions=16, batch_records=1024, batch_bytes=1 << 20, nbatches=1)
+    place = None
     try:
         for k, s in enumerate(sas):
             rc, sid = drv.newsession(s.esp_sa().csp())
             assert rc == 0 and sid == k
-        outsa = np.zeros(nsa, dtype=OUTSA_DTYPE)
-        enc = np.zeros(nsa, dtype=ENCSA_DTYPE)
-        for k, s in enumerate(sas):
-            outsa[k] = (100 * k, 5000 * k, s.spi, int.from_bytes(s.salt, "little"), L.OUT_PAD_SEQ, 0)
-            enc["flags"][k] = (L.ENC_TUNNEL if tun[k] else 0) | (L.ENC_NATT if natt[k] else 0) | L.ENC_DF_COPY
-            enc["ttl"][k] = 40 + k
-            for f in ("src", "dst"):
-                enc[f][k, :4] = np.frombuffer(EH.addr(rng, False), dtype=np.uint8)
-            if natt[k]:
-                enc["dst"][k, 4:8] = np.frombuffer(struct.pack(">HH", 3000 + k, PORT), dtype=np.uint8)
-        enc["bytes"], enc["packets"] = 1000, 10
-        n = 200
-        sa = rng.integers(0, nsa, n)
-        pkts, protos = [], []
-        for k in sa:
-            proto = int(rng.choice([6, 17, 1]))
-            body = bytearray(rng.integers(0, 256, int(rng.integers(0, 300)), dtype=np.uint8).tobytes())
-            if proto == 17 and len(body) >= 8:
-                body[4:6] = struct.pack(">H", len(body))
-            if tun[k] and rng.random() < 0.3:
-                pkts.append(CH.ipv6(EH.addr(rng, True), body, nxt=proto))
-            else:
-                dst = EH.addr(rng, False) if tun[k] else enc["dst"][k, :4].tobytes()
-                ihl = int(rng.integers(5, 16))
-                pkts.append(CH.ipv4(dst, body, ihl=ihl, proto=proto,
-                                    opts=rng.integers(0, 256, ihl * 4 - 20, dtype=np.uint8).tobytes()))
-            protos.append(proto)
-        head, tail = 72, 49
-        arena, rec = EH.layout(rng, pkts, head, tail)
-        d_arena, d_rec = _up(torch, arena), _up(torch, rec)
+        place = placed(arena, rec) if placed else None
+        if place is None:
+            d_arena = win = _up(torch, arena)
+            d_rec = _up(torch, rec)
+        else:
+            d_arena, win = place.load(arena)                 # win: the layout's bytes inside d_arena
+            d_rec = _up(torch, place.relocate(rec))
         d_sa = torch.from_numpy(sa.astype(np.uint16).view(np.int16).copy()).cuda()
         d_enc, d_outsa = _up(torch, enc), _up(torch, outsa)
         mk = lambda: torch.zeros(n, dtype=torch.uint8, device="cuda")        # noqa: E731
@@ -550,8 +585,9 @@ def test_outbound_then_inbound_end_to_end_with_natt(policy):
         esp_sent(drv, d_opkt, d_desc, st, n, d_enc)
         torch.cuda.synchronize()
         assert not st.cpu().numpy().any(), (est.cpu().numpy(), fst.cpu().numpy(), st.cpu().numpy())
-        wire = d_arena.cpu().numpy()
-        opkt, desc = d_opkt.cpu().numpy().view(PKT_DTYPE), d_desc.cpu().numpy().view(DESC)
+        wire = win.cpu().numpy()
+        opkt = _back(place, d_opkt.cpu().numpy().view(PKT_DTYPE))
+        desc = _back(place, d_desc.cpu().numpy().view(DESC))
         g_enc = d_enc.cpu().numpy().view(ENCSA_DTYPE)
         for k in range(nsa):
             m = sa == k
@@ -599,10 +635,10 @@ def test_outbound_then_inbound_end_to_end_with_natt(policy):
         replay_merge(drv, ist, dst, n)
         torch.cuda.synchronize()
         assert not ist.cpu().numpy().any(), (cst.cpu().numpy(), rst.cpu().numpy(), ist.cpu().numpy(), dst.cpu().numpy())
-        idesc = d_idesc.cpu().numpy().view(DESC)
+        idesc = _back(place, d_idesc.cpu().numpy().view(DESC))
         for fld in ("off4", "len", "sa"):
             assert np.array_equal(idesc[fld], desc[fld]), fld
-        out, ipkt, g_cf = d_arena.cpu().numpy(), d_ipkt.cpu().numpy().view(PKT_DTYPE), cf.cpu().numpy()
+        out, ipkt, g_cf = win.cpu().numpy(), _back(place, d_ipkt.cpu().numpy().view(PKT_DTYPE)), cf.cpu().numpy()
         fixed = valid = 0
         for i, p in enumerate(pkts):
             k = sa[i]
@@ -622,3 +658,5 @@ def test_outbound_then_inbound_end_to_end_with_natt(policy):
             assert g_in["pad_"][k] == delta[k]
     finally:
         drv.close()
+        if place is not None:
+            place.finish()
