@@ -21,7 +21,7 @@ ESPGPU_HD inline uint32_t key_u32hash(uint32_t spi) {
   return h;
 }
 
-constexpr uint32_t kClsKnown = ESPGPU_CLS_IPCSUM | 0xffff0000u;   // and ESPGPU_CLS_NATT_PORT's bits
+constexpr uint32_t kClsKnown = ESPGPU_CLS_IPCSUM | ESPGPU_CLS_AH | 0xffff0000u;   // and ESPGPU_CLS_NATT_PORT's bits
 
 ESPGPU_HD inline uint32_t cls_bswap32(uint32_t x) { return __builtin_bswap32(x); }
 // the big-endian 16-bit field in the low / the high half of a memory-order dword
@@ -55,12 +55,12 @@ ESPGPU_HD inline ClsSlotHead cls_slot_head(const espgpu_sad_entry *e) {
 
 // Probe from the SPI's home slot to a match or a free slot, at most nslots
 // steps (key_allocsa, key.c:1091-1133: the SPI first, then protocol, family
-// and destination).  dst[] is the packet's destination in memory-order
+// and destination).  proto is the packet's, 50 or 51; dst[] is its destination in memory-order
 // dwords, one for af 4 and four for af 6.  True: *sa and *salt are the entry's,
 // *eflags its flags and, for an ESPGPU_SAD_NATT entry, *ports its dst[4..7]
 // (natt->sport, natt->dport as they lie in a UDP header's first dword).
-ESPGPU_HD inline bool cls_find(const espgpu_sad_entry *table, uint32_t nslots, uint32_t spi, uint32_t af,
-                               const uint32_t dst[4], uint32_t *sa, uint32_t *salt, uint32_t *eflags,
+ESPGPU_HD inline bool cls_find(const espgpu_sad_entry *table, uint32_t nslots, uint32_t spi, uint32_t proto,
+                               uint32_t af, const uint32_t dst[4], uint32_t *sa, uint32_t *salt, uint32_t *eflags,
                                uint32_t *ports) {
   if (spi == 0) return false;
   const uint32_t mask = nslots - 1;
@@ -70,7 +70,7 @@ ESPGPU_HD inline bool cls_find(const espgpu_sad_entry *table, uint32_t nslots, u
     if (h.spi == 0) return false;
     if (h.spi != spi) continue;
     // SPIs are unique in the table: this entry decides
-    if (h.ids >> 16 != (50u | af << 8)) return false;
+    if (h.ids >> 16 != (proto | af << 8)) return false;
     const uint8_t *ed = table[slot].dst;
     for (uint32_t j = 0; j < (af == 4 ? 1u : 4u); ++j)
       if (mem_ld32(ed + 4 * j) != dst[j]) return false;
@@ -86,7 +86,7 @@ ESPGPU_HD inline bool cls_find(const espgpu_sad_entry *table, uint32_t nslots, u
 ESPGPU_HD inline bool cls_lookup(const espgpu_sad_entry *table, uint32_t nslots, uint32_t spi, uint32_t af,
                                  const uint32_t dst[4], uint32_t *sa, uint32_t *salt) {
   uint32_t eflags, ports;
-  return cls_find(table, nslots, spi, af, dst, sa, salt, &eflags, &ports);
+  return cls_find(table, nslots, spi, 50, af, dst, sa, salt, &eflags, &ports);
 }
 
 // espgpu_esp_classify's rule; *desc is written in every case.  `table` usable
@@ -96,6 +96,7 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
   int st = ESPGPU_EINVAL;
   uint32_t skip = 0, rlen = 0, af = 0, spi = 0, sa = 0, salt = 0, dst[4] = {0, 0, 0, 0};
   uint32_t udp = 0, uports = 0;                        // a UDP-encapsulated packet and its port dword
+  uint32_t ah = 0;                                     // an AH packet (only under ESPGPU_CLS_AH)
   do {
     if (len < 20) break;
     // the 20 bytes every packet has, in one round of loads
@@ -140,6 +141,14 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
         skip = hlen + 8;
         rlen = ulen - 8;
         dst[0] = w4;
+      } else if (ip_p == 51 && (flags & ESPGPU_CLS_AH)) {
+        st = ESPGPU_EINVAL;
+        if (ip_len - hlen < 12) break;                 // struct newah up to the ICV (the header's 2b)
+        ah = 1;
+        af = 4;
+        skip = hlen;
+        rlen = ip_len;
+        dst[0] = w4;
       } else {
         if (ip_p != 50) break;
         st = ESPGPU_EINVAL;
@@ -158,20 +167,28 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
       st = ESPGPU_EINVAL;
       if (40 + plen > len) break;
       st = ESPGPU_ENOTSUP;
-      if (((w1 >> 16) & 0xffu) != 50) break;           // ip6_nxt
+      const uint32_t nxt = (w1 >> 16) & 0xffu;         // ip6_nxt
+      ah = nxt == 51 && (flags & ESPGPU_CLS_AH);
+      if (nxt != 50 && !ah) break;
       for (uint32_t j = 0; j < 4; ++j) dst[j] = mem_ld32(pkt + 24 + 4 * j);
       if ((dst[0] & 0xc0ffu) == 0x80feu) break;        // fe80::/10
       st = ESPGPU_EINVAL;
-      if (plen < 8 || (plen & 3)) break;
+      if (ah) {
+        if (plen < 12) break;
+        st = ESPGPU_ENOTSUP;
+        if (40 + plen > 65535) break;                  // espgpu_desc.len has 16 bits
+      } else if (plen < 8 || (plen & 3)) {
+        break;
+      }
       af = 6;
       skip = 40;
-      rlen = plen;
+      rlen = ah ? 40 + plen : plen;
     } else {
       break;
     }
-    spi = cls_bswap32(mem_ld32(pkt + skip));
+    spi = cls_bswap32(mem_ld32(pkt + skip + 4 * ah));  // ipsec_input.c:144-153
     uint32_t eflags = 0, eports = 0;
-    st = cls_find(table, nslots, spi, af, dst, &sa, &salt, &eflags, &eports) ? 0 : ESPGPU_ENOENT;
+    st = cls_find(table, nslots, spi, 50 + ah, af, dst, &sa, &salt, &eflags, &eports) ? 0 : ESPGPU_ENOENT;
     if (st == 0 && udp) {                              // udpencap.c:173-181
       if (!(eflags & ESPGPU_SAD_NATT) || eports != uports) st = ESPGPU_ENOENT;
     } else if (st == 0 && (eflags & ESPGPU_SAD_NATT)) {
@@ -180,7 +197,9 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
     }
   } while (0);
   espgpu_desc d;
-  d.off4 = st ? off4 : off4 + skip / 4;
+  // an AH record is the whole packet, with the ICV field's offset as its salt
+  if (ah) salt = skip + 12;
+  d.off4 = (st || ah) ? off4 : off4 + skip / 4;
   d.len = st ? (uint16_t)0 : (uint16_t)rlen;
   d.sa = st ? (uint16_t)0xffffu : (uint16_t)sa;
   d.esn_hi = 0;

@@ -27,6 +27,22 @@ struct DecapPlan {
   uint32_t nxt, q;
 };
 
+// Checks 2 and 3 of espgpu_esp_decap: what ipsec4/6_common_input_cb make of
+// next header nxt with q bytes behind the stripped header.  Shared with the AH
+// decapsulation (ah_in.h).
+ESPGPU_HD inline int dcp_mode(uint32_t flags, uint32_t nxt, uint32_t q, bool *tunnel) {
+  const uint32_t mode = flags & (ESPGPU_IN_TRANSPORT | ESPGPU_IN_TUNNEL);
+  const bool inner4 = nxt == 4 && mode != ESPGPU_IN_TRANSPORT, inner6 = nxt == 41 && mode != ESPGPU_IN_TRANSPORT;
+  *tunnel = false;
+  if (inner4 || inner6) {                            // ipsec_input.c:334-355, :539-562
+    if (q < (inner4 ? 20u : 40u)) return ESPGPU_EINVAL;
+    *tunnel = true;
+  } else if (!(flags & ESPGPU_IN_AF6) && mode == ESPGPU_IN_TUNNEL) {   // :411-416; ipsec6's protocol loop has no such end
+    return ESPGPU_EPFNOSUPPORT;
+  }
+  return 0;
+}
+
 // Checks 1-3 of espgpu_esp_decap.  hlen = 8 + ivlen is the caller's.
 ESPGPU_HD inline int dcp_plan(uint32_t flags, uint32_t hlen, uint32_t alen, uint32_t skip, uint32_t rlen,
                               uint32_t trailer, DecapPlan *p) {
@@ -46,14 +62,8 @@ ESPGPU_HD inline int dcp_plan(uint32_t flags, uint32_t hlen, uint32_t alen, uint
   const uint32_t nxt = trailer & 0xffu, padlen = (trailer >> 8) & 0xffu;
   if (padlen + 2 > plen) return ESPGPU_EINVAL;       // a word that lacks the BADLEN it should carry
   const uint32_t q = plen - padlen - 2;                                          // m_adj, :633
-  const bool inner4 = nxt == 4 && mode != ESPGPU_IN_TRANSPORT, inner6 = nxt == 41 && mode != ESPGPU_IN_TRANSPORT;
-  bool tunnel = false;
-  if (inner4 || inner6) {                            // ipsec_input.c:334-355, :539-562
-    if (q < (inner4 ? 20u : 40u)) return ESPGPU_EINVAL;
-    tunnel = true;
-  } else if (!af6 && mode == ESPGPU_IN_TUNNEL) {     // :411-416; ipsec6's protocol loop has no such end
-    return ESPGPU_EPFNOSUPPORT;
-  }
+  bool tunnel;
+  if (const int st = dcp_mode(flags, nxt, q, &tunnel)) return st;
   p->transport = !tunnel;
   p->off = tunnel ? skip + hlen : hlen + u;
   p->len = tunnel ? q : skip - u + q;

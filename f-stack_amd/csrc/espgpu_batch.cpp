@@ -4,7 +4,8 @@
 // frame.h's, natt.h's and replay.h's), and the host-to-host pipeline.
 #include "espgpu_ctx.h"
 
-#include "classify.h"      // (after the HIP runtime's vector types)
+#include "ah_in.h"         // (after the HIP runtime's vector types)
+#include "classify.h"
 #include "decap.h"
 #include "encap.h"
 #include "frame.h"
@@ -444,6 +445,58 @@ int espgpu_esp_decap_batch(espgpu_ctx *c, const uint8_t *d_arena, uint8_t *d_out
   return run_stage(c, n, 0, nullptr, "decap kernel launch failed", [&] {
     return launch_esp_decap(d_arena, d_out, d_pkt, d_desc, d_trailer, d_status, n, d_in, nin, c->d_sas,
                             c->cfg.max_sessions, d_ipkt, d_dstatus, stream);
+  });
+}
+
+// ---- inbound AH -----------------------------------------------------------------
+// ah_input's checks and ah_massage_headers for one packet, and ah_input_cb's
+// tail with ipsec4/6_common_input_cb.  The rules espgpu_ah_input_batch and
+// espgpu_ah_decap_batch apply (ah_in.h).
+static bool ah_mlen_ok(uint32_t mlen) { return mlen >= 4 && mlen <= 64 && !(mlen & 3); }
+
+int espgpu_ah_input(const espgpu_insa *in, uint32_t mlen, uint8_t *pkt, uint32_t len, uint32_t salt,
+                    uint8_t *hsave) {
+  if (!in || !pkt || !hsave || !ah_mlen_ok(mlen)) return ESPGPU_EINVAL;
+  return ah_input_rule(in->flags, mlen, pkt, len, salt, hsave);
+}
+
+int espgpu_ah_input_batch(espgpu_ctx *c, uint8_t *d_arena, espgpu_desc *d_desc, uint32_t n, const espgpu_insa *d_in,
+                          uint32_t nin, uint8_t *d_hsave, uint8_t *d_astatus, void *stream) {
+  if (!c) return ESPGPU_EINVAL;
+  if (n && (!d_arena || !d_desc || !d_hsave || !d_astatus || (nin && !d_in) || ((uintptr_t)d_arena & 3) ||
+            ((uintptr_t)d_hsave & 3)))
+    return ESPGPU_EINVAL;
+  // no workspace; of the ctx only the session table is read
+  return run_stage(c, n, 0, nullptr, "AH input kernel launch failed", [&] {
+    return launch_ah_input(d_arena, d_desc, n, d_in, nin, c->d_sas, c->cfg.max_sessions, d_hsave, d_astatus, stream);
+  });
+}
+
+int espgpu_ah_decap(espgpu_insa *in, uint32_t mlen, uint8_t *pkt, uint32_t len, uint32_t salt, const uint8_t *hsave,
+                    uint32_t *out_off, uint32_t *out_len) {
+  if (out_off) *out_off = 0;
+  if (out_len) *out_len = 0;
+  if (!in || !pkt || !hsave || !out_off || !out_len || !ah_mlen_ok(mlen)) return ESPGPU_EINVAL;
+  DecapPlan p;
+  const int st = ah_decap_rule(in->flags, mlen, pkt, len, salt, hsave, &p);
+  if (st) return st;
+  *out_off = p.off;
+  *out_len = p.len;
+  in->bytes += p.len;                                            // key.c:8429-8445
+  in->packets += 1;
+  return 0;
+}
+
+int espgpu_ah_decap_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_desc *d_desc, const uint8_t *d_status,
+                          uint32_t n, espgpu_insa *d_in, uint32_t nin, const uint8_t *d_hsave, espgpu_pkt *d_ipkt,
+                          uint8_t *d_dstatus, void *stream) {
+  if (!c) return ESPGPU_EINVAL;
+  if (n && (!d_arena || !d_desc || !d_status || !d_hsave || !d_ipkt || !d_dstatus || (nin && !d_in) ||
+            ((uintptr_t)d_arena & 3) || ((uintptr_t)d_hsave & 3)))
+    return ESPGPU_EINVAL;
+  return run_stage(c, n, 0, nullptr, "AH decap kernel launch failed", [&] {
+    return launch_ah_decap(d_arena, d_desc, d_status, n, d_in, nin, c->d_sas, c->cfg.max_sessions, d_hsave, d_ipkt,
+                           d_dstatus, stream);
   });
 }
 

@@ -1,7 +1,7 @@
 // espgpu_internal.h — device-side data layouts shared by the host runtime
 // (espgpu*.cpp) and the HIP kernels (esp_gcm.hip, esp_cbc.hip, esp_ah.hip,
 // plan.hip, sa_group.hip, replay.hip, frame.hip, classify.hip, decap.hip,
-// encap.hip, xfer.hip).
+// ah_in.hip, encap.hip, xfer.hip).
 #pragma once
 #include <stdint.h>
 
@@ -267,6 +267,13 @@ int launch_esp_classify(const uint8_t *arena, const espgpu_pkt *pkt, uint32_t n,
 int launch_esp_decap(const uint8_t *arena, uint8_t *out, const espgpu_pkt *pkt, const espgpu_desc *desc,
                      const uint32_t *trailer, const uint8_t *status, uint32_t n, espgpu_insa *in, uint32_t nin,
                      const DevSA *sas, uint32_t nsas, espgpu_pkt *ipkt, uint8_t *dstatus, void *stream);
+// espgpu_ah_input_batch and espgpu_ah_decap_batch (ah_in.hip; the rules are
+// ah_in.h's); nsas = the capacity of the DevSA table
+int launch_ah_input(uint8_t *arena, espgpu_desc *desc, uint32_t n, const espgpu_insa *in, uint32_t nin,
+                    const DevSA *sas, uint32_t nsas, uint8_t *hsave, uint8_t *astatus, void *stream);
+int launch_ah_decap(uint8_t *arena, const espgpu_desc *desc, const uint8_t *status, uint32_t n, espgpu_insa *in,
+                    uint32_t nin, const DevSA *sas, uint32_t nsas, const uint8_t *hsave, espgpu_pkt *ipkt,
+                    uint8_t *dstatus, void *stream);
 // espgpu_esp_encap_batch and espgpu_esp_sent_batch (encap.hip; the rule is
 // encap.h's); nsas = the capacity of the DevSA table
 int launch_esp_encap(uint8_t *arena, const espgpu_pkt *pkt, const uint16_t *sa, uint32_t n, const espgpu_encsa *enc,

@@ -20,6 +20,8 @@
 //
 // The check is one lane per record: a 16-byte descriptor, the 4-byte sequence
 // number from the record header and one bitmap word; integer compares only.
+// An AH SA's window (ESPGPU_REPLAY_AH) has its number at desc.salt - 4 of the
+// record, which is the whole packet (replay_seq_at).
 //
 // The update is sequential by definition; three facts make it parallel
 // (DESIGN.md 3.4 has the arguments):
@@ -72,6 +74,19 @@ __device__ bool chkreplay(const espgpu_replay &r, const uint32_t *bitmap, uint32
   return !(th + 1 == 0 && !(r.flags & ESPGPU_REPLAY_CYCSEQ));
 }
 
+// Where a record's sequence number lies and whether the record is long enough
+// to hold it: byte 4 of an ESP record; of an AH record (a window with
+// ESPGPU_REPLAY_AH; the record is the whole packet and salt the ICV field's
+// offset) the dword before the ICV field, newah.ah_seq.
+__device__ __forceinline__ bool replay_seq_at(const espgpu_replay &r, const espgpu_desc &d, uint32_t *at) {
+  if (r.flags & ESPGPU_REPLAY_AH) {
+    *at = d.salt - 4;
+    return d.salt >= 12 && d.salt <= d.len;
+  }
+  *at = 4;
+  return d.len >= 8;
+}
+
 __global__ __launch_bounds__(256) void replay_check_kernel(const uint8_t *arena, espgpu_desc *desc, uint32_t n,
                                                            const espgpu_replay *rp, uint32_t nrp,
                                                            const uint32_t *bitmap, uint8_t *rstatus) {
@@ -79,10 +94,11 @@ __global__ __launch_bounds__(256) void replay_check_kernel(const uint8_t *arena,
   if (i >= n) return;
   const espgpu_desc d = desc[i];
   uint8_t st = 0;
-  if (d.sa < nrp && d.len >= 8) {
+  if (d.sa < nrp && d.len != 0) {
     const espgpu_replay r = rp[d.sa];
-    if (r.wsize != 0) {                        // esp_input: replay != NULL && wsize != 0
-      const uint32_t seq = bswap32(*reinterpret_cast<const uint32_t *>(arena + (size_t)d.off4 * 4 + 4));
+    uint32_t at;
+    if (replay_seq_at(r, d, &at) && r.wsize != 0) {   // esp_input: replay != NULL && wsize != 0
+      const uint32_t seq = bswap32(*reinterpret_cast<const uint32_t *>(arena + (size_t)d.off4 * 4 + at));
       uint32_t seqh = 0;
       if (!chkreplay(r, bitmap, seq, &seqh)) {
         st = ESPGPU_EACCES;
@@ -143,9 +159,10 @@ __global__ __launch_bounds__(256) void upd_prep_kernel(UpdArgs a) {
   const espgpu_desc d = a.desc[i];
   uint32_t k = a.nsa;
   uint8_t u = 0;
-  if (a.status[i] == 0 && d.sa < a.nrp && d.len >= 8) {
+  if (a.status[i] == 0 && d.sa < a.nrp && d.len != 0) {
     const espgpu_replay r = a.rp[d.sa];
-    if (r.wsize != 0) {
+    uint32_t at;
+    if (replay_seq_at(r, d, &at) && r.wsize != 0) {
       if (replay_usable64(r)) k = d.sa;
       else u = ESPGPU_EINVAL;
     }
@@ -249,8 +266,10 @@ __global__ __launch_bounds__(256) void upd_scan_kernel(UpdArgs a) {
       } else {
         if (key[j] < a.nsa) {
           const espgpu_desc d = a.desc[a.order[p]];
-          const uint32_t seq = bswap32(*reinterpret_cast<const uint32_t *>(a.arena + (size_t)d.off4 * 4 + 4));
-          s[j] = (a.rp[key[j]].flags & ESPGPU_REPLAY_ESN) ? ((uint64_t)d.esn_hi << 32) | seq : seq;
+          const uint32_t rflags = a.rp[key[j]].flags;
+          const uint32_t at = (rflags & ESPGPU_REPLAY_AH) ? d.salt - 4 : 4u;
+          const uint32_t seq = bswap32(*reinterpret_cast<const uint32_t *>(a.arena + (size_t)d.off4 * 4 + at));
+          s[j] = (rflags & ESPGPU_REPLAY_ESN) ? ((uint64_t)d.esn_hi << 32) | seq : seq;
         }
         a.w.sseq[p] = s[j];
       }

@@ -86,6 +86,7 @@ class Replay(C.Structure):
 
 
 REPLAY_ESN, REPLAY_CYCSEQ, EACCES = 0x1, 0x2, 13
+REPLAY_AH = 0x4                  # an AH SA's window: the sequence number is at desc.salt - 4
 
 
 class OutSA(C.Structure):
@@ -116,6 +117,7 @@ class SadEntry(C.Structure):
 
 CLS_IPCSUM, ENOENT, ENOTSUP = 0x1, 2, 95
 SAD_NATT = 0x2
+CLS_AH = 0x4                     # classify ip_p / ip6_nxt 51 packets too
 
 
 def CLS_NATT_PORT(port):
@@ -133,6 +135,8 @@ class InSA(C.Structure):
 INSA_DTYPE = np.dtype([("bytes", "<u8"), ("packets", "<u8"), ("flags", "<u4"), ("pad_", "<u4")])
 IN_TRANSPORT, IN_TUNNEL, IN_PAD_RAND, IN_AF6 = 0x1, 0x2, 0x4, 0x8
 IN_NATT, NATT_CSUM_VALID = 0x20, 0x1
+IN_AH, IN_AH_KEEPTOS = 0x40, 0x80
+AH_SAVE_SLOT = 64                # bytes of d_hsave per record (espgpu_ah_input_batch)
 ENODATA, EPFNOSUPPORT = 61, 96
 
 
@@ -242,6 +246,12 @@ def lib():
                                                 C.POINTER(C.c_uint8)]
             L.espgpu_esp_natt_cksum_batch.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32,
                                                       C.c_uint32, vp, vp]
+        if hasattr(L, "espgpu_ah_input_batch"):         # (absent from older builds used in A/B runs)
+            L.espgpu_ah_input.argtypes = [C.POINTER(InSA), C.c_uint32, vp, C.c_uint32, C.c_uint32, vp]
+            L.espgpu_ah_input_batch.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
+            L.espgpu_ah_decap.argtypes = [C.POINTER(InSA), C.c_uint32, vp, C.c_uint32, C.c_uint32, vp,
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+            L.espgpu_ah_decap_batch.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
         L.espgpu_last_kernel_ms.argtypes = [vp]
         L.espgpu_last_kernel_ms.restype = C.c_float
         L.espgpu_set_tuning.argtypes = [vp, C.c_char_p, C.c_int]

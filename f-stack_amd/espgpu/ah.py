@@ -8,6 +8,15 @@
   ah_input_crp()      ah_input               xform_ah.c:613-664
   ah_input_cb()       ah_input_cb's compare  xform_ah.c:735-749
   ah_output_crp()     ah_output              xform_ah.c:972-1047
+The inbound AH stages of the device-resident batch path (include/espgpu.h, the
+inbound AH block) are restated here on bytes:
+  ipsec_input_classify_ah()  ip_input / ip6_input, ipsec_common_input for ip_p 51
+                                             ipsec_input.c:141-208
+  ah_hdrsiz()         ah_hdrsiz              xform_ah.c:144-169
+  ah_input()          ah_input's length checks, save and massage
+                                             xform_ah.c:576-600, :628-650
+  ah_input_cb_decap() ah_input_cb after the compare, then
+                      esp.ipsec_common_input_cb   xform_ah.c:758-814
 Packets are IP packets with the AH header (struct newah: next header, length,
 reserved, SPI, sequence number, then the ICV) at `skip`, in a bytearray or an
 mbuf-like list of bytearrays.
@@ -84,13 +93,15 @@ def _copyback(pkt, off, data):
             return
 
 
-def ah_massage_ipv4(pkt, skip, out):
+def ah_massage_ipv4(pkt, skip, out, cleartos=True):
     """ah_massage_headers for AF_INET, on the first `skip` bytes (the IP
-    header with its options) of `pkt`: TOS (ah_cleartos), TTL, checksum and
-    the fragment field zeroed; the option loop.  -> the massaged header
-    (bytes); raises ValueError where the kernel answers EINVAL."""
+    header with its options) of `pkt`: TOS (if cleartos: V_ah_cleartos, 1 by
+    default), TTL, checksum and the fragment field zeroed; the option loop.
+    -> the massaged header (bytes); raises ValueError where the kernel answers
+    EINVAL."""
     ptr = bytearray(_flat(pkt)[:skip])
-    ptr[1] = 0                              # ip_tos (V_ah_cleartos = 1)
+    if cleartos:
+        ptr[1] = 0                          # ip_tos (V_ah_cleartos)
     ptr[8] = 0                              # ip_ttl
     ptr[10:12] = b"\0\0"                    # ip_sum
     ptr[6:8] = b"\0\0"                      # ip_off
@@ -121,10 +132,11 @@ def ah_massage_ipv4(pkt, skip, out):
     return bytes(ptr[:skip])
 
 
-def ah_massage_ipv6(pkt):
+def ah_massage_ipv6(pkt, cleartos=True):
     """ah_massage_headers for AF_INET6, the basic header only: flow label and
     traffic class, hop limit zeroed, version kept; link-local scope ids
-    cleared.  -> the massaged 40-byte header."""
+    cleared.  cleartos changes nothing here: ip6_flow is zeroed whatever
+    V_ah_cleartos says (:410).  -> the massaged 40-byte header."""
     h = bytearray(_flat(pkt)[:40])
     if h[4:6] == b"\0\0":
         raise ValueError("unsupported IPv6 jumbogram")
@@ -196,3 +208,146 @@ def ah_output_crp(fw, ses, sa, pkt, skip, esn_hi=0):
     crp = _digest_crp(fw, ses, sa, pkt, skip, esn_hi)
     crp.crp_opaque = saved
     return crp
+
+
+# ---- the inbound AH stages of the device-resident batch path --------------------
+IPPROTO_ESP = 50
+
+
+def ipsec_input_classify_ah(sadb, pkt, off4=0, ipcsum=False, port=0):
+    """esp.ipsec_input_classify_natt with the AH branch: what the stack does
+    with a received ip_p / ip6_nxt 51 packet up to ah_input's first lines.
+    ip_input's / ip6_input's checks as for ESP, then ipsec_common_input: the
+    length check, here against struct newah up to the ICV (12 bytes; the
+    reference answers EINVAL below 8, ipsec_input.c:141, and ENOBUFS from
+    ah_input's pullup for 8..11: one code, EINVAL, is the engine's deliberate
+    difference), the SPI at skip + 4 (:151-153) and key_allocsa with proto 51.
+    No alignment check: that is esp_input's.  An IPv6 packet whose 40 + plen
+    does not fit the descriptor's 16-bit length is the host stack's
+    (ENOTSUP).  The descriptor of an accepted AH packet is the DIGEST record
+    of the batch path: (off4, whole length, sa, 0, skip + 12).  Every other
+    packet goes through esp.ipsec_input_classify_natt unchanged."""
+    from . import esp as E
+    raw = bytes(pkt)
+    n = len(raw)
+    v = raw[0] >> 4 if n >= 20 else 0
+    isah = (v == 4 and raw[9] == IPPROTO_AH) or (v == 6 and n >= 40 and raw[6] == IPPROTO_AH)
+    if not isah:
+        return E.ipsec_input_classify_natt(sadb, raw, off4, ipcsum, port)
+    def drop(status):
+        return status, (off4, 0, 0xffff, 0, 0)
+
+    if v == 4:
+        hlen = (raw[0] & 0xf) << 2
+        if hlen < 20 or hlen > n:
+            return drop(L.EINVAL)
+        if ipcsum and E.in_cksum(raw[:hlen]) != 0:
+            return drop(L.EINVAL)
+        ip_len, ip_off = struct.unpack(">H", raw[2:4])[0], struct.unpack(">H", raw[6:8])[0]
+        if ip_len < hlen or n < ip_len:
+            return drop(L.EINVAL)
+        raw = raw[:ip_len]                                           # the trim, ip_input.c:555-561
+        if ip_off & 0x3fff:                                          # IP_MF | IP_OFFMASK: ip_reass, the host's
+            return drop(L.ENOTSUP)
+        af, skip, dst = 4, hlen, raw[16:20]
+    else:
+        plen = struct.unpack(">H", raw[4:6])[0]
+        if plen == 0:                                                # jumbo payload option
+            return drop(L.ENOTSUP)
+        if n - 40 < plen:                                            # ip6s_tooshort
+            return drop(L.EINVAL)
+        raw = raw[:40 + plen]
+        af, skip, dst = 6, 40, raw[24:40]
+        if dst[0] == 0xfe and dst[1] & 0xc0 == 0x80:                 # IN6_IS_SCOPE_LINKLOCAL
+            return drop(L.ENOTSUP)
+    if len(raw) - skip < AhSecAssoc.rplen:                           # ipsec_input.c:141 / ah_input's pullup
+        return drop(L.EINVAL)
+    if len(raw) > 65535:                                             # espgpu_desc.len
+        return drop(L.ENOTSUP)
+    spi = struct.unpack(">I", raw[skip + 4:skip + 8])[0]             # ipsec_input.c:151-153
+    sav = sadb.get(spi) if spi else None
+    if sav is None:
+        return drop(L.ENOENT)
+    sa, proto, saf, sdst = sav[:4]
+    if proto != IPPROTO_AH or saf != af or bytes(sdst)[:len(dst)] != dst:    # key.c:1110-1118
+        return drop(L.ENOENT)
+    return 0, (off4, len(raw), sa, 0, skip + AhSecAssoc.rplen)
+
+
+def ah_hdrsiz(mlen, af6):
+    """ah_hdrsiz (xform_ah.c:144-169): roundup(HDRSIZE + AUTHSIZE, 4), or 8 for
+    an AF_INET6 SA (RFC 4302)."""
+    align = 8 if af6 else 4
+    return (AhSecAssoc.rplen + mlen + align - 1) // align * align
+
+
+def ah_input(af6, mlen, packet_bytes, skip, cleartos=True):
+    """ah_input on bytes, without the replay check and the crypto request:
+    the header-length checks (xform_ah.c:576-600), the save (:632) and
+    ah_massage_headers with out = 0 (:641).  Returns (status, the packet with
+    its first skip bytes massaged, the first skip bytes as they arrived), or
+    (status, None, None) for a packet that is dropped.  What ah_input's
+    callers guarantee is checked first, with EINVAL: skip as ip_input /
+    ip6_input leave it, a header whose own length and version agree with it,
+    and struct newah inside the packet."""
+    m = bytes(packet_bytes)
+    if skip % 4 or (skip != 40 if af6 else not 20 <= skip <= 60) or len(m) < skip + AhSecAssoc.rplen:
+        return L.EINVAL, None, None
+    if (m[0] >> 4 != 6) if af6 else (m[0] != 0x40 | skip >> 2):
+        return L.EINVAL, None, None
+    hl = 8 + m[skip + 1] * 4                                         # sizeof(struct ah) + ah_len * 4, :577
+    ahsize = ah_hdrsiz(mlen, af6)
+    if hl != ahsize:                                                 # :581
+        return L.EACCES, None, None
+    if skip + ahsize > len(m):                                       # :591
+        return L.EACCES, None, None
+    saved = m[:skip]
+    if af6:
+        if m[4:6] == b"\0\0":                                        # :404
+            return L.EMSGSIZE, None, None
+        hdr = ah_massage_ipv6(m, cleartos)
+    else:
+        try:
+            hdr = ah_massage_ipv4(m, skip, 0, cleartos)
+        except ValueError:
+            return L.EINVAL, None, None
+    return 0, hdr + m[skip:], saved
+
+
+def ah_input_cb_decap(mode, af6, mlen, packet_bytes, saved, skip):
+    """ah_input_cb after the compare and the window update (xform_ah.c:758-814)
+    and ipsec4/6_common_input_cb (esp.ipsec_common_input_cb) with one packet
+    that ah_input accepted: `packet_bytes` as ah_input left it, `saved` the
+    first skip bytes it saved.  mode is saidx.mode (esp.IPSEC_MODE_*).
+    Returns (status, resulting packet bytes, bytes key_sa_recordxfer books)."""
+    from . import esp as E
+    m = bytes(packet_bytes)
+    ahsize = ah_hdrsiz(mlen, af6)
+    nxt = m[skip]                                                    # ah_nxt, saved at :638
+    ptr = bytearray(saved[:skip])
+    protoff = 6 if af6 else 9
+    ptr[protoff] = nxt                                               # :759
+    m = bytes(ptr) + m[skip:]                                        # m_copyback, :762
+    m = m[:skip] + m[skip + ahsize:]                                 # m_striphdr, :791
+    return E.ipsec_common_input_cb(mode, af6, m, skip, nxt)
+
+
+def ah_input_host(insa, mlen, buf, length, salt, hsave, at=0):
+    """espgpu_ah_input, the engine's host rule, on a bytearray that holds the
+    packet at `at`, an L.InSA and a bytearray save slot: returns the status."""
+    import ctypes as C
+    raw = (C.c_uint8 * (len(buf) - at)).from_buffer(buf, at) if len(buf) > at else None
+    hs = (C.c_uint8 * len(hsave)).from_buffer(hsave)
+    return L.lib().espgpu_ah_input(C.byref(insa), mlen, C.cast(raw, C.c_void_p), length, salt, C.cast(hs, C.c_void_p))
+
+
+def ah_decap_host(insa, mlen, buf, length, salt, hsave, at=0):
+    """espgpu_ah_decap, the engine's host rule: returns (status, out_off,
+    out_len)."""
+    import ctypes as C
+    raw = (C.c_uint8 * (len(buf) - at)).from_buffer(buf, at)
+    hs = (C.c_uint8 * len(hsave)).from_buffer(hsave)
+    off, ln = C.c_uint32(0xdddddddd), C.c_uint32(0xdddddddd)
+    rc = L.lib().espgpu_ah_decap(C.byref(insa), mlen, C.cast(raw, C.c_void_p), length, salt, C.cast(hs, C.c_void_p),
+                                 C.byref(off), C.byref(ln))
+    return rc, off.value, ln.value

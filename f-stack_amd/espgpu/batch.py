@@ -171,7 +171,8 @@ def esp_classify(driver, arena, pkt, n, table, desc, cstatus, flags=0, stream=No
     rest of the inbound sequence, and cstatus 0 / EINVAL / ENOTSUP / ENOENT,
     for replay_merge at its end; a refused packet's descriptor has len 0 and
     sa 0xffff.  flags: L.CLS_IPCSUM, L.CLS_NATT_PORT(port) to take ESP in UDP
-    to that port."""
+    to that port, L.CLS_AH to take AH packets (their descriptor is the whole
+    packet, with the ICV field's offset as its salt)."""
     for t in (arena, pkt, table, desc, cstatus):
         assert t.is_cuda and t.is_contiguous()
     assert pkt.numel() >= n * PKT_DTYPE.itemsize and desc.numel() * desc.element_size() >= n * 16
@@ -209,6 +210,51 @@ def esp_decap(driver, arena, out, pkt, desc, trailer, status, n, insa, ipkt, dst
         status.data_ptr(), n, insa.data_ptr(), nin, ipkt.data_ptr(), dstatus.data_ptr(), _stream_ptr(stream))
     if rc:
         raise RuntimeError("espgpu_esp_decap_batch: %s (%d)" % (driver.last_error(), rc))
+
+
+def ah_input(driver, arena, desc, n, insa, hsave, astatus, stream=None):
+    """ah_input's header-length checks and ah_massage_headers between
+    esp_classify (with L.CLS_AH) and replay_check (espgpu_ah_input_batch):
+    desc as esp_classify gave it, insa the INSA_DTYPE tensor whose AH SAs carry
+    L.IN_AH, hsave a uint8 CUDA tensor of n * L.AH_SAVE_SLOT bytes.  Every
+    record of a DIGEST session has its IP header saved into its slot and
+    massaged in the arena, or is refused: astatus receives 0 / EINVAL / EACCES
+    / EMSGSIZE per record for replay_merge, and a refused record's descriptor
+    gets len 0.  Records of other sessions are passed over with status 0."""
+    for t in (arena, desc, insa, hsave, astatus):
+        assert t.is_cuda and t.is_contiguous()
+    assert desc.numel() * desc.element_size() >= n * 16 and astatus.numel() >= n
+    assert hsave.element_size() == 1 and hsave.numel() >= n * L.AH_SAVE_SLOT
+    nin = insa.numel() * insa.element_size() // INSA_DTYPE.itemsize
+    rc = driver.lib.espgpu_ah_input_batch(
+        driver.ctx, arena.data_ptr(), desc.data_ptr(), n, insa.data_ptr(), nin, hsave.data_ptr(),
+        astatus.data_ptr(), _stream_ptr(stream))
+    if rc:
+        raise RuntimeError("espgpu_ah_input_batch: %s (%d)" % (driver.last_error(), rc))
+
+
+def ah_decap(driver, arena, desc, status, n, insa, hsave, ipkt, dstatus, stream=None):
+    """ah_input_cb's restore and strip with ipsec4/6_common_input_cb, the last
+    step of the inbound AH sequence before the final replay_merge
+    (espgpu_ah_decap_batch), in place: desc and hsave as ah_input left them,
+    status as decrypt_batch and the merges left it.  A transport record's
+    saved header is written, fixed, just before the payload; a tunnel record's
+    packet is not touched.  ipkt receives one PKT_DTYPE record per AH packet,
+    absolute as esp_classify takes it (length 0 for a refused or failed
+    record; an ESP record's entry is not written), dstatus 0 / EINVAL /
+    EPFNOSUPPORT for replay_merge, and every SA's bytes and packets grow by
+    what was accepted."""
+    for t in (arena, desc, status, insa, hsave, ipkt, dstatus):
+        assert t.is_cuda and t.is_contiguous()
+    assert desc.numel() * desc.element_size() >= n * 16 and status.numel() >= n and dstatus.numel() >= n
+    assert hsave.element_size() == 1 and hsave.numel() >= n * L.AH_SAVE_SLOT
+    assert ipkt.numel() * ipkt.element_size() >= n * PKT_DTYPE.itemsize
+    nin = insa.numel() * insa.element_size() // INSA_DTYPE.itemsize
+    rc = driver.lib.espgpu_ah_decap_batch(
+        driver.ctx, arena.data_ptr(), desc.data_ptr(), status.data_ptr(), n, insa.data_ptr(), nin,
+        hsave.data_ptr(), ipkt.data_ptr(), dstatus.data_ptr(), _stream_ptr(stream))
+    if rc:
+        raise RuntimeError("espgpu_ah_decap_batch: %s (%d)" % (driver.last_error(), rc))
 
 
 def esp_natt_cksum(driver, out, ipkt, desc, trailer, status, dstatus, n, insa, policy=0, cflags=None, stream=None):

@@ -398,7 +398,16 @@ def esp_input_decap(mode, af6, prand, ivlen, alen, packet_bytes, skip):
     m = m[:len(m) - (lastthree[1] + 2)]                              # m_adj, :633
     protoff = 6 if af6 else 9                                        # ip6_nxt / ip_p
     m = m[:protoff] + lastthree[2:3] + m[protoff + 1:]               # m_copyback, :636
-    prot = lastthree[2]
+    return ipsec_common_input_cb(mode, af6, m, skip, lastthree[2])
+
+
+def ipsec_common_input_cb(mode, af6, m, skip, prot):
+    """ipsec4_common_input_cb / ipsec6_common_input_cb up to netisr_queue
+    (ipsec_input.c:298-417, :531-638) on the packet `m` as the transform's
+    callback hands it over: the outer header of `skip` bytes with its protocol
+    field already `prot`, and the payload behind it.  Shared by esp_input_decap
+    and ah.ah_input_cb_decap.  Returns (status, resulting packet bytes, bytes
+    key_sa_recordxfer books)."""
     if not af6:                                                      # ipsec4_common_input_cb
         ip = bytearray(m[:skip])
         ip[2:4] = struct.pack(">H", len(m) & 0xffff)                 # ip_len, :312

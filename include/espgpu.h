@@ -48,6 +48,8 @@ extern "C" {
 #define ESPGPU_ABI_VERSION 6
 #define ESPGPU_HAS_NATT 1   /* the NAT-T block below is built; the ABI version stays: new symbols and
                              flag bits that were refused before, no layout change */
+#define ESPGPU_HAS_AH_BATCH 1   /* the inbound AH block below is built (ESPGPU_CLS_AH, ESPGPU_REPLAY_AH,
+                                 espgpu_ah_input, espgpu_ah_decap); the ABI version stays, as above */
 
 /* ---- constants, numerically identical to freebsd/opencrypto/cryptodev.h ---- */
 #define ESPGPU_CSP_MODE_CIPHER      2        /* cryptodev.h:362: ESP without auth */
@@ -285,7 +287,8 @@ int  espgpu_get_stats(espgpu_ctx *ctx, struct espgpu_stats *st);
  * field inside it (a multiple of 4, salt + mlen <= len; else EINVAL).  In
  * both directions the ICV field reads as zeros while the packet is hashed
  * (ah_input's save-and-zero, ah_output's zeroing); the mutable IP header
- * fields are the caller's business (ah_massage_headers).  encrypt: the ICV is
+ * fields are the caller's business (ah_massage_headers; inbound,
+ * espgpu_ah_input_batch does it on the device: the inbound AH block below).  encrypt: the ICV is
  * written at salt, status 0, nothing else moves.  decrypt (and _trailer): the
  * stored ICV is compared (ah_input_cb), status 0 or EBADMSG, and nothing is
  * written to d_arena or d_out, in place or out of place; the trailer word is
@@ -382,9 +385,19 @@ int  espgpu_decrypt_host(espgpu_ctx *ctx, const uint8_t *h_arena, uint64_t arena
  *                                  a caller with such SAs
  *   6. espgpu_replay_merge         with 5's: (d_status, d_dstatus, n).
  * espgpu_replay_update / _update64 are the same update on the host, one
- * record per call. */
+ * record per call.  AH records have a sequence of their own (the inbound AH
+ * block below).
+ *
+ * ESPGPU_REPLAY_AH marks the window of an AH SA.  An AH record is the whole
+ * packet, so byte 4 of it is ip_id / ip_off; for a window with this flag the
+ * check and the update read the sequence number big-endian at byte
+ * desc.salt - 4 of the record (newah.ah_seq, directly before the ICV field),
+ * and the record takes part if 12 <= desc.salt <= desc.len, in place of len >=
+ * 8.  Windows without the flag behave as before; the host functions take the
+ * sequence number as an argument and ignore the flag. */
 #define ESPGPU_REPLAY_ESN    0x1     /* SADB_X_SAFLAGS_ESN  */
 #define ESPGPU_REPLAY_CYCSEQ 0x2     /* SADB_X_EXT_CYCSEQ   */
+#define ESPGPU_REPLAY_AH     0x4     /* the sequence number is at desc.salt - 4 (xform_ah.c:565, :776) */
 #define ESPGPU_EACCES        13      /* replayed (esp_input's EACCES, esps_replay) */
 struct espgpu_replay {
 	uint64_t last;
@@ -577,6 +590,7 @@ struct espgpu_sad_entry {      /* 32 B: one slot of the SPI table; spi == 0: fre
 };
 #define ESPGPU_CLS_IPCSUM 0x1  /* verify the IPv4 header checksum (ip_input.c:518-530) */
 #define ESPGPU_SAD_NATT   0x2  /* sav->natt != NULL (keydb.h:94-103): proto 50, af 4 only */
+#define ESPGPU_CLS_AH     0x4  /* classify ip_p / ip6_nxt 51 packets too (2b, 3b below); clear: ENOTSUP */
 /* Bits 16-31 of the classification flags: the local UDP encapsulation port in
  * host order (the socket with UF_ESPINUDP, udp_usrreq.c:335); 0: off. */
 #define ESPGPU_CLS_NATT_PORT(p) ((uint32_t)((p) & 0xffffu) << 16)
@@ -623,6 +637,13 @@ int  espgpu_sad_build(const struct espgpu_sad_entry *sas, uint32_t nsas,
  *      skip = hlen + 8, record length = ulen - 8; after the lookup of 4:
  *      the entry lacks ESPGPU_SAD_NATT, or uh_sport / uh_dport are not
  *        its dst[4..5] / dst[6..7] (udpencap.c:173-181)              ENOENT
+ *  2b. AH, only with ESPGPU_CLS_AH in flags (without it ip_p 51 is ENOTSUP as
+ *      above), after the sanity and fragment checks of 2:
+ *      ip_len - hlen < 12 (struct newah up to the ICV)               EINVAL
+ *        (a deliberate difference, one code before the lookup: the reference
+ *        answers EINVAL below 8, ipsec_input.c:141, and ENOBUFS from ah_input's
+ *        pullup for 8..11, xform_ah.c:551-558.  No & 3 check: that is ESP's.)
+ *      skip = hlen, record length = ip_len: the whole packet
  *   3. IPv6: len < 40                                                EINVAL
  *      payload length 0 (jumbogram)                                  ENOTSUP
  *      40 + plen > len                                               EINVAL
@@ -630,14 +651,23 @@ int  espgpu_sad_build(const struct espgpu_sad_entry *sas, uint32_t nsas,
  *      destination in fe80::/10 (scope, ipsec_input.c:184-189)       ENOTSUP
  *      plen < 8, or plen & 3                                         EINVAL
  *      skip = 40, record length = plen
- *   4. the SPI (big-endian dword at skip) is 0, no slot holds it, or the
- *      slot's proto != 50, its af is not the packet's, or its dst is
- *      not the packet's destination (4 or 16 bytes)                  ENOENT
+ *  3b. AH, only with ESPGPU_CLS_AH: next header 51 passes the next-header row
+ *      and the fe80::/10 row of 3, then
+ *      plen < 12                                                     EINVAL
+ *      40 + plen > 65535 (espgpu_desc.len has 16 bits)               ENOTSUP
+ *      skip = 40, record length = 40 + plen
+ *   4. the SPI (big-endian dword at skip; for AH at skip + 4,
+ *      ipsec_input.c:151-153) is 0, no slot holds it, or the slot's proto is
+ *      not the packet's (50, or 51 for AH), its af is not the packet's, or its
+ *      dst is not the packet's destination (4 or 16 bytes)           ENOENT
  *      a plain ip_p 50 packet whose entry has ESPGPU_SAD_NATT        ENOTSUP
  *        (a deliberate difference: ipsec_common_input would take it, but the
  *        later steps tell a UDP-encapsulated packet by its SA alone, so the
  *        host stack decides)
- * Fragments, AH, UDP-encapsulated ESP with a nonzero UDP checksum, NAT-T
+ *   An accepted AH packet's descriptor is {off4, record length, entry.sa, 0,
+ *   skip + 12}: the DIGEST record of the batch path, the whole packet with the
+ *   ICV field's offset in salt; the entry's salt is ignored for proto 51.
+ * Fragments, AH without ESPGPU_CLS_AH, UDP-encapsulated ESP with a nonzero UDP checksum, NAT-T
  * keepalives, IKE and everything else answered ENOTSUP are the host stack's
  * packets; IPv6 NAT-T does not exist in the reference either.  Not re-checked: the per-transform lengths (the decrypt kernels'
  * EINVAL), whether session `sa` exists (theirs too), loopback and other
@@ -676,6 +706,10 @@ int  espgpu_esp_classify_batch(espgpu_ctx *ctx, const uint8_t *d_arena,
                                      by the SA's family, :638-648); clear: AF_INET           */
 #define ESPGPU_IN_NATT      0x20  /* sav->natt != NULL: the packet came UDP-encapsulated
                                      (the NAT-T block below); AF_INET only                   */
+#define ESPGPU_IN_AH        0x40  /* an AH SA: espgpu_ah_input / espgpu_ah_decap take it (the inbound
+                                     AH block below); espgpu_esp_decap refuses it                */
+#define ESPGPU_IN_AH_KEEPTOS 0x80 /* V_ah_cleartos == 0: ip_tos is hashed as it came; clear (the
+                                     reference default): zeroed.  Only with ESPGPU_IN_AH        */
 #define ESPGPU_ENODATA      61    /* next header IPPROTO_NONE: RFC 4303 2.6 dummy, dropped   */
 #define ESPGPU_EPFNOSUPPORT 96    /* ipsec4_common_input_cb: "cannot handle inner ip proto"  */
 struct espgpu_insa {              /* 24 B, indexed by session id, lives in device memory     */
@@ -993,6 +1027,124 @@ int  espgpu_esp_natt_cksum_batch(espgpu_ctx *ctx, uint8_t *d_out, const struct e
                                  const uint8_t *d_status, const uint8_t *d_dstatus, uint32_t n,
                                  const struct espgpu_insa *d_in, uint32_t nin, uint32_t policy,
                                  uint8_t *d_cflags, void *stream);
+
+/* ---- inbound AH (ah_input, ah_massage_headers with out = 0 and ah_input_cb
+ *      after the compare: freebsd/netipsec/xform_ah.c:144-169, :261-525,
+ *      :576-600, :628-650, :758-814; then ipsec4/6_common_input_cb and
+ *      key_sa_recordxfer as the decapsulation block states them) ----
+ * IPv4 with options and IPv6 without extension headers (those packets stay
+ * the host stack's: classification answers ENOTSUP for them).  The inbound AH
+ * sequence on a device-resident batch, all on one stream:
+ *   0. espgpu_esp_classify_batch with ESPGPU_CLS_AH
+ *   1. espgpu_ah_input_batch         header-length checks, save, massage
+ *   2. espgpu_replay_check_batch     windows with ESPGPU_REPLAY_AH
+ *   3. espgpu_decrypt_batch_trailer  the digest kernel: ICV field read as zeros, compared
+ *   4. espgpu_replay_update_batch
+ *   5. espgpu_replay_merge four times, in this order: 1's result, 2's, 4's,
+ *      0's.  A later merge overrides an earlier one: replay goes over 1's
+ *      result, as ah_input checks replay first.  (A record that 1 refused has
+ *      len 0 and takes no part in 2, so a replayed packet with bad options
+ *      ends with 1's EINVAL where the reference answers EACCES: dropped
+ *      either way, and without a window lookup.)
+ *   6. espgpu_ah_decap_batch         restore, strip, mode, SA lifetime counters
+ *   7. espgpu_replay_merge           with 6's result.
+ * An ESP record in the same batch passes through 1 and 6 untouched with status
+ * 0; an AH record passes through espgpu_esp_decap_batch with EINVAL.  The
+ * per-SA state is struct espgpu_insa with ESPGPU_IN_AH (and the mode bits,
+ * ESPGPU_IN_AF6, ESPGPU_IN_AH_KEEPTOS).
+ *
+ * Host: ah_input's checks and ah_massage_headers for one packet of `len` bytes
+ * at `pkt` (the record a DIGEST descriptor names: len = desc.len, salt =
+ * desc.salt), mlen the session's ICV length (a multiple of 4, 4..64; else
+ * EINVAL).  With skip = salt - 12 the checks in order; the first that fires
+ * decides, and a refused packet has nothing written, neither to pkt nor to
+ * hsave (the reference zeroes a malformed option before it frees the packet):
+ *   1. flags without ESPGPU_IN_AH, with ESPGPU_IN_PAD_RAND or ESPGPU_IN_NATT,
+ *      with unknown bits, or with both mode bits                     EINVAL
+ *      salt < 32, or skip & 3                                        EINVAL
+ *      AF_INET: version nibble not 4 or ip_hl * 4 != skip            EINVAL
+ *      AF6: version nibble not 6 or skip != 40                       EINVAL
+ *      len < skip + 12                                               EINVAL
+ *   2. ahsize = roundup(12 + mlen, AF6 ? 8 : 4) (ah_hdrsiz, :144-169)
+ *      8 + ah_len * 4 != ahsize (:581)                               EACCES
+ *      skip + ahsize > len (:591)                                    EACCES
+ *   3. IPv4 (:291-393): ip_tos (unless ESPGPU_IN_AH_KEEPTOS), ip_ttl, ip_sum
+ *      and ip_off are zeroed, then the option loop from byte 20 to skip:
+ *      an option other than EOL or NOP at off + 1 >= skip (:303-312) EINVAL
+ *      EOL ends the loop, NOP is one byte
+ *      an option length < 2 (:329, :344, :370)                       EINVAL
+ *      options 0x82, 0x85, 0x86, 0x94 and 0x95 are kept, every other option
+ *        is zeroed, type and length bytes too (:378-381)
+ *      an option running past skip (:386)                            EINVAL
+ *      IPv6 (:401-422): ip6_plen == 0                                EMSGSIZE
+ *      ip6_flow = 0 with the version kept, ip6_hlim = 0; s6_addr16[1] of a
+ *      link-local (fe80::/10) source or destination zeroed
+ *   4. hsave[0, skip) receives the first skip bytes as they arrived (the
+ *      front of xform_data, :632); hsave[skip, 64) is not written.  The
+ *      massaged header goes over the packet's.  Every header byte is loaded
+ *      before any is stored.  The ICV stays where it is: the digest kernel
+ *      reads the field as zeros and compares (:635, :745-749).
+ * The AH header itself and everything behind it is never written.  Null
+ * pointers are EINVAL. */
+int  espgpu_ah_input(const struct espgpu_insa *in, uint32_t mlen, uint8_t *pkt, uint32_t len,
+                     uint32_t salt, uint8_t *hsave);
+/* The same rule for a device-resident batch, between the classification and
+ * the replay check.  Record i takes part if d_desc[i].len != 0, d_desc[i].sa <
+ * nin and the ctx holds a DIGEST session with that id; mlen is that session's,
+ * the packet the d_desc[i].len bytes at d_arena + d_desc[i].off4 * 4 and its
+ * save slot d_hsave + i * 64.  d_astatus[i] is the rule's status.  A refused
+ * record also gets d_desc[i].len = 0, so the later stages pass over it.  Any
+ * other record (an ESP session's, a refused one of an earlier stage) gets
+ * d_astatus[i] = 0 and nothing else written.  d_arena and d_hsave are 4-byte
+ * aligned (EINVAL otherwise); d_hsave holds n * 64 bytes.  One lane per
+ * packet; a wave none of whose packets has IPv4 options does not run the
+ * option loop.  Asynchronous on the caller's stream, no workspace, no host
+ * round trip; n == 0 is a no-op that returns 0. */
+int  espgpu_ah_input_batch(espgpu_ctx *ctx, uint8_t *d_arena, struct espgpu_desc *d_desc, uint32_t n,
+                           const struct espgpu_insa *d_in, uint32_t nin, uint8_t *d_hsave,
+                           uint8_t *d_astatus, void *stream);
+/* Host: ah_input_cb after the compare and the window update, for one packet
+ * that espgpu_ah_input accepted and whose ICV verified: pkt, len, salt and
+ * mlen as there, hsave the slot it filled.  nxt = pkt[skip] (ah_nxt; the AH
+ * header was never massaged), q = len - skip - ahsize.  The checks in order;
+ * a refused packet has nothing written, books nothing and gets *out_off =
+ * *out_len = 0:
+ *   1. the flag, skip and length rows of espgpu_ah_input's check 1 (the
+ *      version row is 3's), and len < skip + ahsize                  EINVAL
+ *   2. tunnel, transport or EPFNOSUPPORT, q < 20 / q < 40: steps 2 and 3 of
+ *      espgpu_esp_decap, with this nxt and q.
+ *   3. transport: the saved header, with its protocol field (byte 9; IPv6:
+ *      byte 6) set to nxt (:759), goes to pkt + ahsize (:762, m_striphdr :791);
+ *      ip_len = skip + q with ip_sum recomputed, or ip6_plen = q, exactly as
+ *      step 5 of espgpu_esp_decap; a saved header whose version / ip_hl do not
+ *      agree with skip is EINVAL.  The result is {ahsize, skip + q} and the SA
+ *      books as many bytes.
+ *      tunnel: the packet is not touched.  The result is {skip + ahsize, q}
+ *      and the SA books q bytes.
+ *   4. accepted: in->bytes += booked, in->packets += 1.
+ * A packet that does not come through both functions and the compare with
+ * status 0 is a dropped packet: its first skip bytes in the arena stay
+ * massaged, and the original header remains in hsave. */
+int  espgpu_ah_decap(struct espgpu_insa *in, uint32_t mlen, uint8_t *pkt, uint32_t len, uint32_t salt,
+                     const uint8_t *hsave, uint32_t *out_off, uint32_t *out_len);
+/* The same rule for a device-resident batch, in place (the digest writes no
+ * d_out), after the merges of step 5.  Record i takes part if d_status[i] ==
+ * 0, d_desc[i].sa < nin, the ctx holds a DIGEST session with that id and the
+ * SA has ESPGPU_IN_AH.  d_dstatus[i] is the rule's status and d_ipkt[i] =
+ * {d_desc[i].off4 + out_off / 4, out_len}: absolute, in the form
+ * espgpu_esp_classify_batch takes, so AH transport around ESP goes straight
+ * back into classification.  A record with d_status[i] != 0 gets d_dstatus[i]
+ * = 0 and d_ipkt[i] = {d_desc[i].off4, 0}.  A record with status 0 of an ESP
+ * session the ctx holds gets d_dstatus[i] = 0 and its d_ipkt[i] is not
+ * written (espgpu_esp_decap_batch's result may stand there); any other record
+ * with status 0 gets EINVAL and the empty d_ipkt[i].  The counters are summed
+ * as espgpu_esp_decap_batch's.  d_arena and d_hsave are 4-byte aligned (EINVAL
+ * otherwise).  Asynchronous on the caller's stream, no workspace, no host
+ * round trip; n == 0 is a no-op that returns 0. */
+int  espgpu_ah_decap_batch(espgpu_ctx *ctx, uint8_t *d_arena, const struct espgpu_desc *d_desc,
+                           const uint8_t *d_status, uint32_t n, struct espgpu_insa *d_in, uint32_t nin,
+                           const uint8_t *d_hsave, struct espgpu_pkt *d_ipkt, uint8_t *d_dstatus,
+                           void *stream);
 
 /* Device time of the last timed batch's crypto kernels (ms, from HIP events
  * on the batch stream).  Process-path batches of <= 128 KiB (a burst on its
