@@ -5,6 +5,7 @@
 #include "espgpu_ctx.h"
 
 #include "ah_in.h"         // (after the HIP runtime's vector types)
+#include "ah_out.h"
 #include "classify.h"
 #include "decap.h"
 #include "encap.h"
@@ -582,6 +583,81 @@ int espgpu_esp_sent_batch(espgpu_ctx *c, const espgpu_pkt *d_opkt, const espgpu_
   if (!c || (n && (!d_opkt || !d_desc || !d_status || (nenc && !d_enc)))) return ESPGPU_EINVAL;
   return run_stage(c, n, 0, nullptr, "sent kernel launch failed", [&] {
     return launch_esp_sent(d_opkt, d_desc, d_status, n, d_enc, nenc, stream);
+  });
+}
+
+// ---- outbound AH ----------------------------------------------------------------
+// The transport-or-tunnel decision, ipsec_encap and ah_output's header work
+// with ah_massage_headers (out = 1) for one packet, ah_output's sequence number
+// and ah_output_cb's restore with key_sa_recordxfer.  The rules
+// espgpu_ah_encap_batch, espgpu_ah_frame_batch and espgpu_ah_sent_batch apply
+// (ah_out.h).
+int espgpu_ah_encap(const espgpu_encsa *e, uint32_t mlen, uint8_t *pkt, uint32_t len, uint32_t headroom,
+                    uint16_t ip_id, uint8_t *hsave, uint32_t *out_front, uint32_t *out_total, uint32_t *out_salt) {
+  for (uint32_t *r : {out_front, out_total, out_salt})
+    if (r) *r = 0;
+  if (!e || !pkt || !hsave || !out_front || !out_total || !out_salt) return ESPGPU_EINVAL;
+  AhOutPlan p;
+  const int st = ah_encap_rule(e, mlen, pkt, len, headroom, ip_id, hsave, &p);
+  if (st) return st;
+  *out_front = p.ahsize + p.oh;
+  *out_total = p.total;
+  *out_salt = (p.tunnel ? p.oh : p.skip) + 12;
+  return 0;
+}
+
+int espgpu_ah_frame(espgpu_outsa *o, uint8_t *pkt, uint32_t len, uint32_t salt, uint32_t *esn_hi) {
+  if (!o || !pkt || !esn_hi) return ESPGPU_EINVAL;
+  return ah_frame_rule(o, pkt, len, salt, esn_hi);
+}
+
+int espgpu_ah_sent(espgpu_encsa *e, uint8_t status, uint8_t *pkt, uint32_t len, uint32_t salt,
+                   const uint8_t *hsave) {
+  if (!e || !pkt || !hsave) return ESPGPU_EINVAL;
+  if (status != 0 || !(e->flags & ESPGPU_ENC_AH)) return 0;
+  const int st = ah_sent_rule(e->flags, pkt, len, salt, hsave);
+  if (st) return st;
+  e->bytes += len;                                               // key.c:8429-8445
+  e->packets += 1;
+  return 0;
+}
+
+int espgpu_ah_encap_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_pkt *d_pkt, const uint16_t *d_sa, uint32_t n,
+                          const espgpu_encsa *d_enc, uint32_t nenc, uint32_t headroom, uint32_t id0,
+                          uint8_t *d_hsave, espgpu_desc *d_desc, espgpu_pkt *d_opkt, uint8_t *d_estatus,
+                          void *stream) {
+  if (!c) return ESPGPU_EINVAL;
+  if (n && (!d_arena || !d_pkt || !d_sa || !d_hsave || !d_desc || !d_opkt || !d_estatus || (nenc && !d_enc) ||
+            ((uintptr_t)d_arena & 3) || ((uintptr_t)d_hsave & 3)))
+    return ESPGPU_EINVAL;
+  // no workspace; of the ctx only the session table is read
+  return run_stage(c, n, 0, nullptr, "AH encap kernel launch failed", [&] {
+    return launch_ah_encap(d_arena, d_pkt, d_sa, n, d_enc, nenc, c->d_sas, c->cfg.max_sessions, headroom, id0,
+                           d_hsave, d_desc, d_opkt, d_estatus, stream);
+  });
+}
+
+int espgpu_ah_frame_batch(espgpu_ctx *c, uint8_t *d_arena, espgpu_desc *d_desc, uint32_t n, espgpu_outsa *d_out,
+                          uint32_t nout, uint8_t *d_fstatus, void *stream) {
+  if (!c || (n && (!d_arena || !d_desc || !d_fstatus || (nout && !d_out) || ((uintptr_t)d_arena & 3))))
+    return ESPGPU_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  return run_stage(c, n, ah_frame_workspace_bytes(std::max(n, 1024u), nout), st, "AH frame launch failed", [&] {
+    return launch_ah_frame(d_arena, d_desc, n, d_out, nout, c->d_sas, c->cfg.max_sessions, d_fstatus, c->d_stage_ws,
+                           st);
+  });
+}
+
+int espgpu_ah_sent_batch(espgpu_ctx *c, uint8_t *d_arena, const espgpu_pkt *d_opkt, const espgpu_desc *d_desc,
+                         const uint8_t *d_status, uint32_t n, espgpu_encsa *d_enc, uint32_t nenc,
+                         const uint8_t *d_hsave, uint8_t *d_sstatus, void *stream) {
+  if (!c) return ESPGPU_EINVAL;
+  if (n && (!d_arena || !d_opkt || !d_desc || !d_status || !d_hsave || !d_sstatus || (nenc && !d_enc) ||
+            ((uintptr_t)d_arena & 3) || ((uintptr_t)d_hsave & 3)))
+    return ESPGPU_EINVAL;
+  return run_stage(c, n, 0, nullptr, "AH sent kernel launch failed", [&] {
+    return launch_ah_sent(d_arena, d_opkt, d_desc, d_status, n, d_enc, nenc, c->d_sas, c->cfg.max_sessions, d_hsave,
+                          d_sstatus, stream);
   });
 }
 

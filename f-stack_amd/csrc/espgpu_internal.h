@@ -285,6 +285,18 @@ int launch_esp_natt_cksum(uint8_t *out, const espgpu_pkt *ipkt, const espgpu_des
                           uint32_t nin, uint32_t policy, uint32_t lanes, uint8_t *cflags, void *stream);
 int launch_esp_sent(const espgpu_pkt *opkt, const espgpu_desc *desc, const uint8_t *status, uint32_t n,
                     espgpu_encsa *enc, uint32_t nenc, void *stream);
+// espgpu_ah_encap_batch, espgpu_ah_frame_batch and espgpu_ah_sent_batch
+// (ah_out.hip; the rules are ah_out.h's); nsas = the capacity of the DevSA
+// table, ws = ah_frame_workspace_bytes(n, nout) bytes (monotonic in both)
+int launch_ah_encap(uint8_t *arena, const espgpu_pkt *pkt, const uint16_t *sa, uint32_t n, const espgpu_encsa *enc,
+                    uint32_t nenc, const DevSA *sas, uint32_t nsas, uint32_t headroom, uint32_t id0, uint8_t *hsave,
+                    espgpu_desc *desc, espgpu_pkt *opkt, uint8_t *estatus, void *stream);
+size_t ah_frame_workspace_bytes(uint32_t n, uint32_t nout);
+int launch_ah_frame(uint8_t *arena, espgpu_desc *desc, uint32_t n, espgpu_outsa *out, uint32_t nout,
+                    const DevSA *sas, uint32_t nsas, uint8_t *fstatus, void *ws, void *stream);
+int launch_ah_sent(uint8_t *arena, const espgpu_pkt *opkt, const espgpu_desc *desc, const uint8_t *status, uint32_t n,
+                   espgpu_encsa *enc, uint32_t nenc, const DevSA *sas, uint32_t nsas, const uint8_t *hsave,
+                   uint8_t *sstatus, void *stream);
 #ifdef ESPGPU_BOUNDS
 // The bounds-checked build's host side (`make checked` only: libespgpu.so
 // exports none of it and include/espgpu.h does not declare it; bounds_chk.h).

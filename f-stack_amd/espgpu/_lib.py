@@ -153,6 +153,7 @@ ENCSA_DTYPE = np.dtype([("bytes", "<u8"), ("packets", "<u8"), ("flags", "<u4"), 
 ENC_TUNNEL, ENC_AF6, ENC_DF_SET, ENC_DF_COPY = 0x01, 0x02, 0x04, 0x08
 ENC_ECN_ALLOWED, ENC_ECN_NOCARE, ENC_RFC6864 = 0x10, 0x20, 0x40
 ENC_NATT = 0x200
+ENC_AH, ENC_AH_KEEPTOS = 0x80, 0x100     # an AH SA (the outbound AH block); V_ah_cleartos == 0
 EMSGSIZE, EAFNOSUPPORT, ENOBUFS = 90, 97, 105
 
 
@@ -252,6 +253,16 @@ def lib():
             L.espgpu_ah_decap.argtypes = [C.POINTER(InSA), C.c_uint32, vp, C.c_uint32, C.c_uint32, vp,
                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
             L.espgpu_ah_decap_batch.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp, vp]
+        if hasattr(L, "espgpu_ah_encap_batch"):         # (absent from older builds used in A/B runs)
+            u32p = C.POINTER(C.c_uint32)
+            L.espgpu_ah_encap.argtypes = [C.POINTER(EncSA), C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint16, vp,
+                                          u32p, u32p, u32p]
+            L.espgpu_ah_frame.argtypes = [C.POINTER(OutSA), vp, C.c_uint32, C.c_uint32, u32p]
+            L.espgpu_ah_sent.argtypes = [C.POINTER(EncSA), C.c_uint8, vp, C.c_uint32, C.c_uint32, vp]
+            L.espgpu_ah_encap_batch.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32,
+                                                vp, vp, vp, vp, vp]
+            L.espgpu_ah_frame_batch.argtypes = [vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
+            L.espgpu_ah_sent_batch.argtypes = [vp, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp]
         L.espgpu_last_kernel_ms.argtypes = [vp]
         L.espgpu_last_kernel_ms.restype = C.c_float
         L.espgpu_set_tuning.argtypes = [vp, C.c_char_p, C.c_int]

@@ -17,6 +17,15 @@ inbound AH block) are restated here on bytes:
                                              xform_ah.c:576-600, :628-650
   ah_input_cb_decap() ah_input_cb after the compare, then
                       esp.ipsec_common_input_cb   xform_ah.c:758-814
+The outbound AH stages (include/espgpu.h, the outbound AH block) likewise:
+  ipsec_output_encap_ah()  ipsec4/6_perform_request, ipsec_encap, ah_output up
+                      to the AH header   ipsec_output.c:221-242, :531-590,
+                                             :882-992; xform_ah.c:855-935
+  ah_output_seq()     ah_output's replay counter and SPI
+                                             xform_ah.c:928, :937-958, :1045-1048
+  ah_output()         the save and ah_massage_headers with out = 1
+                                             xform_ah.c:988, :1027
+  ah_output_cb()      ah_output_cb's m_copyback    xform_ah.c:1120
 Packets are IP packets with the AH header (struct newah: next header, length,
 reserved, SPI, sequence number, then the ICV) at `skip`, in a bytearray or an
 mbuf-like list of bytearrays.
@@ -122,6 +131,8 @@ def ah_massage_ipv4(pkt, skip, out, cleartos=True):
             if ptr[off + 1] < 2:
                 raise ValueError("illegal IPv4 option length for option %d" % o)
             if o in (IPOPT_LSRR, IPOPT_SSRR) and out:
+                if off + ptr[off + 1] > skip:           # (the reference swaps first and refuses at :386)
+                    raise ValueError("malformed IPv4 options header")
                 # the destination the receiver will see: the option's last address
                 ptr[16:20] = ptr[off + ptr[off + 1] - 4:off + ptr[off + 1]]
             count = ptr[off + 1]
@@ -351,3 +362,186 @@ def ah_decap_host(insa, mlen, buf, length, salt, hsave, at=0):
     rc = L.lib().espgpu_ah_decap(C.byref(insa), mlen, C.cast(raw, C.c_void_p), length, salt, C.cast(hs, C.c_void_p),
                                  C.byref(off), C.byref(ln))
     return rc, off.value, ln.value
+
+
+# ---- the outbound AH stages of the device-resident batch path -------------------
+# (include/espgpu.h, the outbound AH block)
+#   ipsec_output_encap_ah()  ipsec4/6_perform_request, ipsec_encap, ah_output up
+#                            to the AH header's first dword and padding, with
+#                            ipsec_process_done's length fields
+#                                 ipsec_output.c:221-242, :531-590, :720-770,
+#                                 :882-992; xform_ah.c:855-935, :1020-1024
+#   ah_output_seq()          ah_output's replay counter   xform_ah.c:928, :937-958, :1045-1048
+#   ah_output()              the save and ah_massage_headers with out = 1
+#                                 xform_ah.c:988, :1027, :291-422
+#   ah_output_cb()           ah_output_cb's m_copyback    xform_ah.c:1120
+def ipsec_output_encap_ah(tunnel, saf6, src, dst, ttl, dfbit, ecn, rfc6864, mlen, packet, headroom, ip_id):
+    """What the stack does with a cleartext packet between ip_output and
+    ah_output's replay counter: the transport-or-tunnel decision and
+    ipsec_encap as esp.ipsec_output_encap restates them, then ah_output's size
+    check (xform_ah.c:882), m_makespace (:907), the AH header's first dword
+    (:925-927), the zeroed padding (:934) and the protocol field (:1020-1024),
+    with ipsec_process_done's length fields and ip_output's checksum in the IP
+    header in front of it.  Arguments as esp.ipsec_output_encap, mlen the ICV
+    length.  Returns (status, front, wire, hs, nxt): the wire packet starts
+    front bytes before where the cleartext packet started, `wire` holds it
+    with None for every byte the step leaves to others (SPI, sequence number,
+    ICV field), hs is the length of the IP header in front of the AH header
+    and nxt is ah_nxt.  (status, 0, None, 0, 0) for a packet that is dropped.
+    The lengths come from len(packet) (the reference adds ahsize to the field
+    as it stands, :1001, :1012); a packet longer than 65535 bytes is EMSGSIZE
+    and link-local SA addresses are ENOTSUP, as for ESP."""
+    from . import esp as E
+    m = bytes(packet)
+    src, dst = bytes(src), bytes(dst)
+    alen_a = 16 if saf6 else 4
+    drop = lambda st: (st, 0, None, 0, 0)                            # noqa: E731
+    if mlen % 4 or not 4 <= mlen <= 64:
+        return drop(L.EINVAL)
+    if saf6:
+        if not any(src[:16]) or not any(dst[:16]):                   # ipsec_output.c:961-964
+            return drop(L.EINVAL)
+        if any(a[0] == 0xfe and a[1] & 0xc0 == 0x80 for a in (src, dst)):
+            return drop(L.ENOTSUP)
+    if len(m) < 20:
+        return drop(L.EINVAL)
+    v = m[0] >> 4
+    if v == 4:
+        skip = (m[0] & 0xf) << 2
+        if skip < 20 or skip > len(m):
+            return drop(L.EINVAL)
+        protoff, pdst = 9, m[16:20]
+    elif v == 6:
+        if len(m) < 40:
+            return drop(L.EINVAL)
+        skip, protoff, pdst = 40, 6, m[24:40]                        # :574-581
+    else:
+        return drop(L.EAFNOSUPPORT)                                  # :932-933
+    if len(m) > E.IP_MAXPACKET:
+        return drop(L.EMSGSIZE)
+    encap = (tunnel or saf6 != (v == 6) or                           # :224-228, :543-547
+             (any(dst[:alen_a]) and dst[:alen_a] != pdst))
+    if encap and not saf6 and (not any(src[:4]) or not any(dst[:4])):    # :938-941
+        return drop(L.EINVAL)
+    ahsize = ah_hdrsiz(mlen, saf6)
+    oh = (40 if saf6 else 20) if encap else 0
+    total = len(m) + ahsize + oh
+    if total > E.IP_MAXPACKET:                                       # xform_ah.c:882
+        return drop(L.EMSGSIZE)
+    if ahsize + oh > headroom:                                       # ipsec_prepend, m_makespace (:907)
+        return drop(L.ENOBUFS)
+    m = bytearray(m)
+    if encap:
+        if v == 4:
+            setdf = dfbit if dfbit in (0, 1) else int(m[6] & 0x40 != 0)          # :910-917
+            itos, proto = m[1], E.IPPROTO_IPIP
+            m[2:4] = struct.pack(">H", len(m))                       # :230
+            m[10:12] = b"\0\0"                                       # :231
+            m[10:12] = struct.pack(">H", E.in_cksum(bytes(m[:skip])))    # :232
+        else:
+            m[4:6] = struct.pack(">H", len(m) - 40)                  # :533
+            itos, proto = (struct.unpack(">I", m[:4])[0] >> 20) & 0xff, E.IPPROTO_IPV6   # :925
+            setdf = 1 if dfbit else 0                                # :926
+        if not saf6:                                                 # :942-956
+            ip_off = E.IP_DF if setdf else 0
+            idv = 0 if rfc6864 and ip_off & E.IP_DF else ip_id & 0xffff          # ip_id.c:252
+            outer = bytearray(struct.pack(">BBHHHBBH4s4s", 0x45, E.ip_ecn_ingress(ecn, itos), len(m) + 20, idv,
+                                          ip_off, ttl, proto, 0, src[:4], dst[:4]))
+        else:                                                        # :965-984
+            outer = bytearray(struct.pack(">IHBB16s16s", 0x60000000 | E.ip_ecn_ingress(ecn, itos) << 20,
+                                          len(m), proto, ttl, src[:16], dst[:16]))
+        m = outer + m
+        skip, protoff = (40, 6) if saf6 else (20, 9)                 # :568-582, :244-260
+    nxt = m[protoff]                                                 # xform_ah.c:925
+    ah = [nxt, (ahsize - 8) // 4, 0, 0] + [None] * 8 + [None] * mlen + [0] * (ahsize - 12 - mlen)   # :925-934
+    wire = list(m[:skip]) + ah + list(m[skip:])                      # m_makespace(m, skip, ahsize), :907
+    wire[protoff] = IPPROTO_AH                                       # :1020-1024
+    assert len(wire) == total
+    if saf6:                                                         # ipsec_process_done, :742
+        wire[4:6] = list(struct.pack(">H", total - 40))
+    else:
+        wire[2:4] = list(struct.pack(">H", total))                   # :727
+        wire[10:12] = [0, 0]
+        wire[10:12] = list(struct.pack(">H", E.in_cksum(bytes(wire[:skip]))))    # ip_output.c:780-782
+    return 0, oh + ahsize, wire, skip, nxt
+
+
+def ah_output(saf6, wire, hs, cleartos=True):
+    """ah_output's save (xform_ah.c:988) and ah_massage_headers with out = 1
+    (:1027) on what ipsec_output_encap_ah returned.  Returns (status, the
+    packet with its first hs bytes massaged, the first hs bytes in wire form),
+    (EINVAL, None, None) where the option loop refuses.  A source-route option
+    shorter than 4 bytes is refused too: the engine's deliberate difference."""
+    saved = bytes(wire[:hs])
+    if saf6:
+        hdr = ah_massage_ipv6(saved, cleartos)                       # ip6_plen != 0: it holds ahsize at least
+    else:
+        try:
+            hdr = ah_massage_ipv4(saved, hs, 1, cleartos)
+        except ValueError:
+            return L.EINVAL, None, None
+        off = 20
+        while off < hs and saved[off] != IPOPT_EOL:                  # the loop accepted these options
+            if saved[off] == IPOPT_NOP:
+                off += 1
+                continue
+            if saved[off] in (IPOPT_LSRR, IPOPT_SSRR) and saved[off + 1] < 4:
+                return L.EINVAL, None, None
+            off += saved[off + 1]
+    return 0, list(hdr) + list(wire[hs:]), saved
+
+
+def ah_output_seq(state, spi, packet, salt):
+    """ah_output's replay counter (xform_ah.c:937-958) and SPI (:928) for the
+    packet whose ICV field is at `salt`, and crp_esn (:1045-1048): `state` is
+    an esp.OutState (count, flags as L.OUT_* bits; ah_output checks the wrap
+    whatever OUT_WRAPCHECK says).  Returns (status, packet, esn_hi, advanced
+    state); (EACCES, None, None, state) at the end of the number space."""
+    st, f = state.copy(), state.flags
+    if not f & L.OUT_CYCSEQ and (st.count == 2**64 - 1 or
+                                 (not f & L.OUT_ESN and st.count & 0xffffffff == 0xffffffff)):   # :940-943
+        return L.EACCES, None, None, state
+    st.count = (st.count + 1) & (2**64 - 1)                          # :956
+    out = list(packet)
+    out[salt - 8:salt] = list(struct.pack(">II", spi, st.count & 0xffffffff))    # :928, :957
+    return 0, out, (st.count >> 32 if f & L.OUT_ESN else 0), st
+
+
+def ah_output_cb(packet, saved):
+    """ah_output_cb's m_copyback (xform_ah.c:1120): the saved header, in wire
+    form, back over the massaged one."""
+    return list(saved) + list(packet[len(saved):])
+
+
+def ah_encap_host(encsa, mlen, buf, at, length, headroom, ip_id, hsave):
+    """espgpu_ah_encap, the engine's host rule, on a bytearray that holds the
+    cleartext packet at `at`, an L.EncSA and a bytearray save slot: returns
+    (status, front, total, salt)."""
+    import ctypes as C
+    raw = (C.c_uint8 * (len(buf) - at)).from_buffer(buf, at) if len(buf) > at else None
+    hs = (C.c_uint8 * len(hsave)).from_buffer(hsave)
+    res = [C.c_uint32(0xdddddddd) for _ in range(3)]
+    rc = L.lib().espgpu_ah_encap(C.byref(encsa), mlen, C.cast(raw, C.c_void_p) if raw else None, length, headroom,
+                                 ip_id & 0xffff, C.cast(hs, C.c_void_p), *[C.byref(r) for r in res])
+    return (rc,) + tuple(r.value for r in res)
+
+
+def ah_frame_host(outsa, buf, at, length, salt, esn_hi=0):
+    """espgpu_ah_frame, the engine's host rule, on a bytearray that holds the
+    wire packet at `at` and an L.OutSA: returns (status, esn_hi), esn_hi as
+    passed in when refused."""
+    import ctypes as C
+    raw = (C.c_uint8 * (len(buf) - at)).from_buffer(buf, at)
+    hi = C.c_uint32(esn_hi)
+    rc = L.lib().espgpu_ah_frame(C.byref(outsa), C.cast(raw, C.c_void_p), length, salt, C.byref(hi))
+    return rc, hi.value
+
+
+def ah_sent_host(encsa, status, buf, at, length, salt, hsave):
+    """espgpu_ah_sent, the engine's host rule: the restore on the bytearray
+    that holds the wire packet at `at` and the booking on the L.EncSA."""
+    import ctypes as C
+    raw = (C.c_uint8 * (len(buf) - at)).from_buffer(buf, at)
+    hs = (C.c_uint8 * len(hsave)).from_buffer(hsave)
+    return L.lib().espgpu_ah_sent(C.byref(encsa), status, C.cast(raw, C.c_void_p), length, salt,
+                                  C.cast(hs, C.c_void_p))

@@ -332,6 +332,70 @@ def esp_sent(driver, opkt, desc, status, n, encsa, stream=None):
         raise RuntimeError("espgpu_esp_sent_batch: %s (%d)" % (driver.last_error(), rc))
 
 
+def ah_encap(driver, arena, pkt, sa, n, encsa, headroom, id0, hsave, desc, opkt, estatus, stream=None):
+    """Outbound AH encapsulation, the step before ah_frame
+    (espgpu_ah_encap_batch): pkt, sa and encsa as esp_encap takes them, the AH
+    SAs' entries carrying L.ENC_AH; hsave a uint8 CUDA tensor of n *
+    L.AH_SAVE_SLOT bytes.  Every packet has headroom writable bytes in front.
+    Transport or tunnel is decided per packet; the header moves or the outer
+    header is built, the AH header's first dword and padding are written, the
+    wire header goes into the packet's slot and its massaged form over the
+    packet.  desc receives the DIGEST record (the whole wire packet, salt = the
+    ICV field's offset) and opkt where the wire packet lies, estatus 0 / EINVAL
+    / ENOTSUP / EAFNOSUPPORT / EMSGSIZE / ENOBUFS for replay_merge; a refused
+    packet's descriptor has len 0 and sa 0xffff."""
+    for t in (arena, pkt, sa, encsa, hsave, desc, opkt, estatus):
+        assert t.is_cuda and t.is_contiguous()
+    assert sa.element_size() == 2 and sa.numel() >= n
+    assert pkt.numel() * pkt.element_size() >= n * PKT_DTYPE.itemsize
+    assert opkt.numel() * opkt.element_size() >= n * PKT_DTYPE.itemsize
+    assert desc.numel() * desc.element_size() >= n * 16 and estatus.numel() >= n
+    assert hsave.element_size() == 1 and hsave.numel() >= n * L.AH_SAVE_SLOT
+    nenc = encsa.numel() * encsa.element_size() // ENCSA_DTYPE.itemsize
+    rc = driver.lib.espgpu_ah_encap_batch(
+        driver.ctx, arena.data_ptr(), pkt.data_ptr(), sa.data_ptr(), n, encsa.data_ptr(), nenc, headroom,
+        id0 & 0xffffffff, hsave.data_ptr(), desc.data_ptr(), opkt.data_ptr(), estatus.data_ptr(),
+        _stream_ptr(stream))
+    if rc:
+        raise RuntimeError("espgpu_ah_encap_batch: %s (%d)" % (driver.last_error(), rc))
+
+
+def ah_frame(driver, arena, desc, n, outsa, fstatus, stream=None):
+    """ah_output's SPI and sequence numbers before encrypt_batch
+    (espgpu_ah_frame_batch): outsa as esp_frame's (count, spi and flags are
+    read).  Each SA's records get their numbers in index order; desc is
+    updated in place (esn_hi; len 0 for refused records) and fstatus receives
+    0 / EINVAL / EACCES (the number space ended) per record, for replay_merge
+    after the encrypt."""
+    for t in (arena, desc, outsa, fstatus):
+        assert t.is_cuda and t.is_contiguous()
+    assert desc.numel() * desc.element_size() >= n * 16 and fstatus.numel() >= n
+    nout = outsa.numel() * outsa.element_size() // OUTSA_DTYPE.itemsize
+    rc = driver.lib.espgpu_ah_frame_batch(
+        driver.ctx, arena.data_ptr(), desc.data_ptr(), n, outsa.data_ptr(), nout, fstatus.data_ptr(),
+        _stream_ptr(stream))
+    if rc:
+        raise RuntimeError("espgpu_ah_frame_batch: %s (%d)" % (driver.last_error(), rc))
+
+
+def ah_sent(driver, arena, opkt, desc, status, n, encsa, hsave, sstatus, stream=None):
+    """ah_output_cb's restore and the SAs' lifetime counters after the
+    outbound merges (espgpu_ah_sent_batch): every record with status 0 of an
+    AH SA gets its wire header back from its slot and books its wire packet's
+    length and one packet into encsa[desc.sa]; sstatus receives 0 / EINVAL."""
+    for t in (arena, opkt, desc, status, encsa, hsave, sstatus):
+        assert t.is_cuda and t.is_contiguous()
+    assert opkt.numel() * opkt.element_size() >= n * PKT_DTYPE.itemsize
+    assert desc.numel() * desc.element_size() >= n * 16 and status.numel() >= n and sstatus.numel() >= n
+    assert hsave.element_size() == 1 and hsave.numel() >= n * L.AH_SAVE_SLOT
+    nenc = encsa.numel() * encsa.element_size() // ENCSA_DTYPE.itemsize
+    rc = driver.lib.espgpu_ah_sent_batch(
+        driver.ctx, arena.data_ptr(), opkt.data_ptr(), desc.data_ptr(), status.data_ptr(), n, encsa.data_ptr(), nenc,
+        hsave.data_ptr(), sstatus.data_ptr(), _stream_ptr(stream))
+    if rc:
+        raise RuntimeError("espgpu_ah_sent_batch: %s (%d)" % (driver.last_error(), rc))
+
+
 def replay_merge(driver, status, rstatus, n, stream=None):
     rc = driver.lib.espgpu_replay_merge(driver.ctx, status.data_ptr(), rstatus.data_ptr(), n,
                                         _stream_ptr(stream))

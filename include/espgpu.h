@@ -50,6 +50,8 @@ extern "C" {
                              flag bits that were refused before, no layout change */
 #define ESPGPU_HAS_AH_BATCH 1   /* the inbound AH block below is built (ESPGPU_CLS_AH, ESPGPU_REPLAY_AH,
                                  espgpu_ah_input, espgpu_ah_decap); the ABI version stays, as above */
+#define ESPGPU_HAS_AH_OUT 1     /* the outbound AH block below is built (ESPGPU_ENC_AH, espgpu_ah_encap,
+                                 espgpu_ah_frame, espgpu_ah_sent); the ABI version stays, as above */
 
 /* ---- constants, numerically identical to freebsd/opencrypto/cryptodev.h ---- */
 #define ESPGPU_CSP_MODE_CIPHER      2        /* cryptodev.h:362: ESP without auth */
@@ -836,7 +838,11 @@ int  espgpu_esp_decap_batch(espgpu_ctx *ctx, const uint8_t *d_arena, uint8_t *d_
 #define ESPGPU_ENC_NATT        0x200 /* sav->natt != NULL: udp_ipsec_output's header (the NAT-T
                                         block below); natt->sport in dst[4..5], natt->dport in
                                         dst[6..7], network order; AF_INET only                 */
-#define ESPGPU_EMSGSIZE     90    /* the result would exceed IP_MAXPACKET (xform_esp.c:747)  */
+#define ESPGPU_ENC_AH          0x80  /* an AH SA: espgpu_ah_encap / espgpu_ah_sent take it (the
+                                        outbound AH block below); EINVAL for espgpu_esp_encap   */
+#define ESPGPU_ENC_AH_KEEPTOS  0x100 /* V_ah_cleartos == 0: ip_tos is hashed as it stands; clear
+                                        (the default): as zero (xform_ah.c:293)                 */
+#define ESPGPU_EMSGSIZE    90    /* the result would exceed IP_MAXPACKET (xform_esp.c:747)  */
 #define ESPGPU_EAFNOSUPPORT 97    /* the packet is neither IPv4 nor IPv6 (ipsec_output.c:933) */
 struct espgpu_encsa {             /* 56 B, indexed by session id, lives in device memory     */
 	uint64_t bytes;               /* lft_c_bytes                                             */
@@ -1145,6 +1151,176 @@ int  espgpu_ah_decap_batch(espgpu_ctx *ctx, uint8_t *d_arena, const struct espgp
                            const uint8_t *d_status, uint32_t n, struct espgpu_insa *d_in, uint32_t nin,
                            const uint8_t *d_hsave, struct espgpu_pkt *d_ipkt, uint8_t *d_dstatus,
                            void *stream);
+
+/* ---- outbound AH (ah_output and ah_output_cb, freebsd/netipsec/xform_ah.c:
+ *      833-1065, :1070-1123, with ah_massage_headers, out = 1, :291-422; around
+ *      them ipsec4/6_perform_request's mode decision, ipsec_encap,
+ *      ipsec_process_done's length fields and key_sa_recordxfer as the
+ *      encapsulation block states them) ----
+ * From cleartext IP packets in the arena to authenticated wire packets.  The
+ * outbound AH sequence on a device-resident batch, all on one stream, no host
+ * round trip:
+ *   1. espgpu_ah_encap_batch   mode, outer header, header move, AH header,
+ *                              save, massage (out = 1); builds d_desc and d_opkt
+ *   2. espgpu_ah_frame_batch   SPI and ah_seq in arrival order per SA, esn_hi;
+ *                              the wrap check
+ *   3. espgpu_encrypt_batch    the digest kernel writes the ICV (unchanged)
+ *   4. espgpu_replay_merge     with 2's result, then with 1's
+ *   5. espgpu_ah_sent_batch    ah_output_cb's m_copyback of the saved header;
+ *                              key_sa_recordxfer
+ * d_opkt is then the list of wire packets, in the form
+ * espgpu_esp_classify_batch takes.  espgpu_esp_encap_batch's d_opkt (after its
+ * own sequence) can be step 1's d_pkt: an ESP-then-AH bundle.  The per-SA state
+ * is struct espgpu_encsa with ESPGPU_ENC_AH (policy, addresses, ttl, lifetime
+ * counters) and, of struct espgpu_outsa, count, spi and flags; both are indexed
+ * by the session id.  IPv4 with options and IPv6 without extension headers, as
+ * inbound.
+ *
+ * Deliberate differences from the reference:
+ *   - An LSRR / SSRR option of length 2 or 3 is EINVAL.  The reference would
+ *     assemble the "last address" (:362-365) from bytes in front of the option,
+ *     as its loop has left them; no receiver can verify such a packet, and
+ *     refusing it keeps the walk free of reads of bytes it has changed.
+ *   - The lengths in the hashed header come from `len`: ip_len = total,
+ *     ip6_plen = total - 40.  The reference adds ahsize to the field as it
+ *     stands (:1001, :1012); the two agree whenever the packet's own length
+ *     field is right.
+ *   - The saved header is in its final wire form, ip_len and ip_sum included;
+ *     the reference leaves these to ipsec_process_done and ip_output, as the
+ *     encapsulation block notes.
+ *   - len > 65535 is EMSGSIZE and fe80::/10 SA addresses are ENOTSUP, as for
+ *     espgpu_esp_encap.
+ *   - SAs without a replay structure are not modelled (the reference leaves
+ *     ah_seq unwritten for them, :939).
+ *   - A packet the option loop refuses consumes no sequence number: the
+ *     massage is step 1 and the numbers are step 2.  (The reference has
+ *     counted by then, :956, :1027; a gap is nothing a receiver can see.)
+ *
+ * Host, step 1: encapsulate one cleartext packet of `len` bytes at `pkt` for
+ * the AH SA `e`; mlen is the session's ICV length, `headroom` the bytes before
+ * pkt that may be written, `ip_id` the value an outer IPv4 header gets, hsave
+ * a 64-byte save slot.  The checks in order; the first that fires decides, and
+ * a refused packet has nothing written, neither to the packet nor to the slot,
+ * and zeros in the three results:
+ *   1. flags with unknown bits, both DF bits or both ECN bits          EINVAL
+ *      ESPGPU_ENC_AH missing                                           EINVAL
+ *      ESPGPU_ENC_NATT set (the reference ignores NAT-T for SAs that
+ *      are not ESP's, key.c:5702)                                      EINVAL
+ *      mlen not a multiple of 4 in 4..64                               EINVAL
+ *      an AF6 SA whose src or dst is unspecified                       EINVAL
+ *      an AF6 SA whose src or dst is in fe80::/10                      ENOTSUP
+ *   2. the packet rows of espgpu_esp_encap's check 2; skip = ip_hl * 4, or 40
+ *      for IPv6, extension headers or not (ipsec_output.c:574-581).
+ *   3. tunnel or transport exactly as espgpu_esp_encap's check 3.
+ *   4. ahsize = roundup(12 + mlen, AF6 SA ? 8 : 4) (ah_hdrsiz); oh = 0, 20 or
+ *      40; total = len + ahsize + oh.
+ *      total > 65535 (xform_ah.c:882)                                  EMSGSIZE
+ *      ahsize + oh > headroom (m_makespace, :907)                      ENOBUFS
+ *   5. tunnel: the inner header is fixed as espgpu_esp_encap's step 5 and the
+ *      outer header built as there, with protocol 51, at pkt - ahsize - oh;
+ *      ah_nxt is 4 or 41.
+ *   6. transport: the skip header bytes move to pkt - ahsize, every dword
+ *      loaded before any is stored; ip_len = total, ip_p = 51 and ip_sum
+ *      recomputed, or ip6_plen = total - 40 and ip6_nxt = 51; ah_nxt is the
+ *      old protocol.
+ *   7. the AH header stands behind that IP header of hs bytes (oh in tunnel
+ *      mode, skip in transport mode): dword 0 is ah_nxt, ah_len = (ahsize - 8)
+ *      / 4, reserve 0 (:925-927).  The SPI and the sequence number are step
+ *      2's.  The zero padding behind the ICV field is written (:934; it is
+ *      hashed); the ICV field itself is not: the digest kernel reads it as
+ *      zeros and then writes it.
+ *   8. hsave[0, hs) receives the IP header in its final wire form, as 5 or 6
+ *      built it: what ah_output_cb copies back.  The packet receives that
+ *      header massaged as ah_massage_headers(out = 1) does: ip_tos (unless
+ *      ESPGPU_ENC_AH_KEEPTOS), ip_ttl, ip_sum and ip_off zeroed, then the
+ *      option loop with the kept and zeroed options and the refusals of
+ *      espgpu_ah_input's check 3.  For LSRR / SSRR (0x83, 0x89) the hashed
+ *      ip_dst becomes the option's last four bytes (:362-365), then the option
+ *      is zeroed; of several such options the last one wins.  IPv6: ip6_flow
+ *      = 0 with the version kept, ip6_hlim = 0, s6_addr16[1] of a link-local
+ *      address zeroed.  A refusal of the option loop is EINVAL and precedes
+ *      every write of 5-8.
+ *   9. *out_front = ahsize + oh: the wire packet is {pkt - *out_front,
+ *      *out_total = total}; *out_salt = hs + 12, the ICV's offset in it.
+ * Null pointers are EINVAL. */
+int  espgpu_ah_encap(const struct espgpu_encsa *e, uint32_t mlen, uint8_t *pkt, uint32_t len,
+                     uint32_t headroom, uint16_t ip_id, uint8_t *hsave, uint32_t *out_front,
+                     uint32_t *out_total, uint32_t *out_salt);
+/* The same rule for n packets of a device-resident arena.  d_pkt[i] is the
+ * cleartext packet and d_sa[i] the SA the caller's SPD lookup chose for it;
+ * d_enc[nenc] is indexed by the session id.  Packet i takes part if d_sa[i] <
+ * nenc and the ctx holds a DIGEST session with that id; mlen is that session's,
+ * the ip_id (uint16_t)(id0 + i) and the save slot d_hsave + i * 64.  headroom
+ * holds for every packet; the caller guarantees that the spans [pkt - headroom,
+ * pkt + len) of one batch lie in the arena and do not overlap.  An accepted
+ * packet gets d_desc[i] = {wire off4, total, sa, 0, hs + 12}, the DIGEST record
+ * of the batch path, d_opkt[i] = {wire off4, total} and d_estatus[i] = 0.  A
+ * refused packet gets its status, one that takes no part (an ESP session's
+ * d_sa, a free slot's) EINVAL, and both d_desc[i] = {d_pkt[i].off4, 0, 0xffff,
+ * 0, 0} and d_opkt[i] = {d_pkt[i].off4, 0}.  d_arena and d_hsave are 4-byte
+ * aligned (EINVAL otherwise); d_hsave holds n * 64 bytes.  One lane per
+ * packet; a wave none of whose packets has IPv4 options does not run the
+ * option loop.  Asynchronous on the caller's stream, no workspace, no host
+ * round trip; n == 0 is a no-op that returns 0. */
+int  espgpu_ah_encap_batch(espgpu_ctx *ctx, uint8_t *d_arena, const struct espgpu_pkt *d_pkt,
+                           const uint16_t *d_sa, uint32_t n, const struct espgpu_encsa *d_enc,
+                           uint32_t nenc, uint32_t headroom, uint32_t id0, uint8_t *d_hsave,
+                           struct espgpu_desc *d_desc, struct espgpu_pkt *d_opkt, uint8_t *d_estatus,
+                           void *stream);
+/* Host, step 2: ah_output's SPI and sequence number (:928, :937-958, :1045-
+ * 1048) for the wire packet of `len` bytes at `pkt` whose ICV field is at
+ * `salt`.  len == 0, salt < 12, salt > len or salt % 4 != 0 is EINVAL.  With
+ * room = what the SA may still give out from o->count (ah_output always
+ * checks, whatever ESPGPU_OUT_WRAPCHECK says, unless ESPGPU_OUT_CYCSEQ is
+ * set): room == 0 is EACCES (:949) with nothing touched.  Otherwise o->count++,
+ * the SPI goes big-endian to salt - 8 and (uint32_t)count to salt - 4, and
+ * *esn_hi = count >> 32 for ESPGPU_OUT_ESN, else 0.  o->cntr, o->salt, the pad
+ * bits and ESPGPU_OUT_CTRCOMPAT mean nothing here and are neither read nor
+ * written.  Null pointers are EINVAL. */
+int  espgpu_ah_frame(struct espgpu_outsa *o, uint8_t *pkt, uint32_t len, uint32_t salt,
+                     uint32_t *esn_hi);
+/* The same rule for a batch, as espgpu_esp_frame_batch: record i takes part if
+ * d_desc[i].len != 0, d_desc[i].sa < nout, the ctx holds a DIGEST session with
+ * that id, 12 <= d_desc[i].salt <= d_desc[i].len and salt % 4 == 0.  The result
+ * is the host rule applied to each SA's taking-part records in index order,
+ * starting from d_out[sa] as it stands; d_desc[i].esn_hi is written and
+ * d_desc[i].salt keeps the ICV offset.  A record refused by the wrap gets
+ * EACCES and d_desc[i].len = 0, and so does the rest of its SA's batch; a
+ * record that takes no part gets EINVAL and d_desc[i].len = 0.  Entries of
+ * SAs with no accepted record are untouched.  The ctx's stage workspace is
+ * shared with espgpu_esp_frame_batch and espgpu_replay_update_batch: ENOMEM
+ * with nothing launched if it cannot grow.  d_arena is 4-byte aligned (EINVAL
+ * otherwise).  n == 0 is a no-op that returns 0. */
+int  espgpu_ah_frame_batch(espgpu_ctx *ctx, uint8_t *d_arena, struct espgpu_desc *d_desc, uint32_t n,
+                           struct espgpu_outsa *d_out, uint32_t nout, uint8_t *d_fstatus,
+                           void *stream);
+/* Host, step 5: ah_output_cb's m_copyback (:1120) and key_sa_recordxfer
+ * (ipsec_output.c:770) for one wire packet that went through with status
+ * `status`: pkt, len and salt as espgpu_ah_encap left them, hsave the slot it
+ * filled.  A nonzero status, or an SA without ESPGPU_ENC_AH, writes nothing,
+ * books nothing and returns 0.  Otherwise hsave[0, salt - 12) goes back over
+ * the packet's first bytes and *e books len bytes and one packet.  salt - 12
+ * not a multiple of 4 in 20..60 (not 40 for an AF6 SA), salt > len, or a slot
+ * whose version nibble does not agree with the SA's family is EINVAL, written
+ * nowhere and booked nowhere.  A dropped packet (one that does not come
+ * through the sequence with status 0) keeps its massaged header in the arena,
+ * and its wire header stays in the slot. */
+int  espgpu_ah_sent(struct espgpu_encsa *e, uint8_t status, uint8_t *pkt, uint32_t len, uint32_t salt,
+                    const uint8_t *hsave);
+/* The same rule for a batch, after the merges.  Record i qualifies if
+ * d_status[i] == 0, d_desc[i].sa < nenc, the ctx holds a DIGEST session with
+ * that id and the SA has ESPGPU_ENC_AH; its packet is the d_opkt[i].len bytes
+ * at d_arena + d_opkt[i].off4 * 4, its salt d_desc[i].salt and its slot
+ * d_hsave + i * 64.  d_sstatus[i] is the rule's status, 0 for every record that
+ * does not qualify (those write nothing and book nothing).  The counters are
+ * summed per wave, and per workgroup where one SA has all of it, before the
+ * 64-bit adds, as espgpu_esp_sent_batch's.  d_arena and d_hsave are 4-byte
+ * aligned (EINVAL otherwise).  Asynchronous on the caller's stream, no
+ * workspace; n == 0 is a no-op that returns 0. */
+int  espgpu_ah_sent_batch(espgpu_ctx *ctx, uint8_t *d_arena, const struct espgpu_pkt *d_opkt,
+                          const struct espgpu_desc *d_desc, const uint8_t *d_status, uint32_t n,
+                          struct espgpu_encsa *d_enc, uint32_t nenc, const uint8_t *d_hsave,
+                          uint8_t *d_sstatus, void *stream);
 
 /* Device time of the last timed batch's crypto kernels (ms, from HIP events
  * on the batch stream).  Process-path batches of <= 128 KiB (a burst on its
