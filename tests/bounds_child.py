@@ -94,6 +94,9 @@ def gcm_runs():
         for fam in S.GCM_FAMILIES:
             runs += [("gcm_mixed[%s] %s" % (fam, design[0]), "S", lambda f=fam: S.gcm_mixed(f), m, True, design)
                      for m in modes]
+        # records up to 65532 bytes, every lane of a wave at a length of its own (about 5 MB; the
+        # uniform long layouts, 44 MiB each, stay with the default library)
+        runs += [("gcm_long_mixed %s" % design[0], "S", S.gcm_long_mixed, m, True, design) for m in modes]
     return runs
 
 

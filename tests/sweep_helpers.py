@@ -1,6 +1,6 @@
 """Shared by the payload-length sweeps (test_length_sweep.py on the CPU,
-test_length_sweep_gpu.py on the GPU): the length sets, the session kinds, the
-batch layouts and the comparison with the oracle.
+test_length_sweep_gpu.py and test_long_records_gpu.py on the GPU): the length
+sets, the session kinds, the batch layouts and the comparison with the oracle.
 
 The kernels choose their code path from a record's length and from the
 lengths of the other records of its wave: the GCM kernels through the wave
@@ -65,6 +65,105 @@ def eta_sa(rng, kind):
 
 def eta_lens(kind):
     return CBC_LENS if kind.startswith("cbc") else CTR_LENS
+
+
+# --- long records: from jumbo size to the largest a descriptor carries -------
+
+MAX_RECORD = 65532                           # len is 16 bits and a multiple of 4
+LONG_ARENA_CAP = 48 << 20                    # every long layout's arena stays below this
+
+
+def gcm_ctr_edge(k):
+    """The GCM counter cache (esp_gcm.hip ctr_cache_build) is keyed on
+    ctr >> 8 and CT block i uses counter i + 2: block 256 k - 2 is the first
+    of key k, and it starts at this payload byte."""
+    return 4096 * k - 32
+
+
+GCM_LONG_KEYS = [3, 4, 7, 8, 15]             # each of the key's four bits on and off
+GCM_JUMBO = list(range(8936, 8961, 4))
+
+
+def gcm_top(mlen):
+    """The largest GCM payload of a session with mlen ICV bytes."""
+    return MAX_RECORD - 16 - mlen
+
+
+def GCM_LONG_LENS(mlen):
+    """Around the key changes of GCM_LONG_KEYS every multiple of 4 in
+    [c_k - 16, c_k + 32] (the last block on either side of the change, at
+    every last-block size), the jumbo window, and the 13 largest payloads."""
+    lens = [L for k in GCM_LONG_KEYS for L in range(gcm_ctr_edge(k) - 16, gcm_ctr_edge(k) + 33, 4)]
+    top = gcm_top(mlen)
+    return sorted(lens + GCM_JUMBO + list(range(top - 48, top + 1, 4)))
+
+
+def gcm_j0_back_key(L):
+    """The 4-lane kernel's aligned schedule (a wave whose records all have
+    nct + 1 a multiple of 4) deals the counter blocks out densely and gives
+    E_K(J0), counter 1, the LAST slot: slot nct, in lane 3 after that lane's CT
+    block nct - 4.  It is the one place where a lane's counter goes back, from
+    this key to key 0 (every other schedule and kernel starts with J0 and
+    counts up).  None for a length the schedule does not take."""
+    nct = gcm_nct(L)
+    return (nct - 2) >> 8 if gcm_aligned(L) and nct >= 4 else None
+
+
+def GCM_LONG_ALIGNED():
+    """nct = 256 k + 3 for the k of GCM_LONG_KEYS, the last block of 4 and of
+    16 bytes: aligned records whose J0 lane steps back from key k.  In
+    GCM_LONG_LENS the aligned lengths just past c_k have nct = 256 k - 1, and
+    that lane is still under key k - 1."""
+    return [16 * (256 * k + 3) - cut for k in GCM_LONG_KEYS for cut in (12, 0)]
+
+
+def gcm_ctr_keys(L):
+    """(the ctr >> 8 values a payload of L bytes runs through, the last CT
+    block's)."""
+    last = (gcm_nct(L) + 1) >> 8
+    return list(range(last + 1)), last
+
+
+def eta_hlen_mlen(kind):
+    """(header bytes in front of the payload, ICV bytes) of a kind, as EtaSA
+    has them."""
+    k = ETA_KINDS[kind]
+    hlen = 16 if k.get("ctr") else 8 if k.get("null") else 24
+    return hlen, 0 if k.get("noauth") else {1: 12, 256: 16, 384: 24, 512: 32}[k["sha"]]
+
+
+def eta_top(kind):
+    """The kind's largest payload: whole blocks for CBC."""
+    hlen, mlen = eta_hlen_mlen(kind)
+    room = MAX_RECORD - hlen - mlen
+    return room // 16 * 16 if kind.startswith("cbc") else room
+
+
+CBC_LONG_NB = list(range(556, 564)) + [1024, 2048]
+
+
+def CBC_LONG_LENS(kind):
+    """Eight consecutive block counts at jumbo size (every residue mod 128 of
+    the hashed length), 1024 and 2048 blocks, and the eight largest."""
+    nbmax = eta_top(kind) // 16
+    return [16 * nb for nb in CBC_LONG_NB + list(range(nbmax - 7, nbmax + 1))]
+
+
+def CTR_LONG_LENS(kind):
+    """AES-CTR and ESP-NULL: every multiple of 4 in the jumbo window, one
+    past 16 KiB and one short of 32 KiB, and the eight largest."""
+    top = eta_top(kind)
+    return list(range(8936, 8965, 4)) + [16388, 32764] + list(range(top - 28, top + 1, 4))
+
+
+def eta_long_lens(kind):
+    return CBC_LONG_LENS(kind) if kind.startswith("cbc") else CTR_LONG_LENS(kind)
+
+
+def arena_bytes(rec_lens, stride_pad=0):
+    """The arena helpers.build_records lays out for records of these lengths
+    (header and ICV included)."""
+    return sum(((int(L) + 3) & ~3) + stride_pad for L in rec_lens) + 64
 
 
 # what the GCM kernels derive from a payload length (esp_gcm.hip do_group)
@@ -483,3 +582,129 @@ def eta_interleaved():
     cts = np.where((sa_idx == 0) | (sa_idx == 3), rng.choice(CBC_LENS[1:], n), rng.choice(CTR_LENS[1:], n))
     tamper = [(int(i), "any") for i in np.nonzero(rng.random(n) < 0.05)[0]]
     return make_batch(rng, sas, sa_idx, cts, tamper, stride_pad=4)
+
+
+# ---------------------------------------------------------------------------
+# long layouts (test_long_records_gpu.py): the length sets above.  A uniform
+# one is about 40 MiB and drags its two oracle arenas along, so ONE long
+# layout is kept at a time, whichever function made it.
+
+_long_slot = {}
+
+
+def _one_long(key, make):
+    if key not in _long_slot:
+        _long_slot.clear()
+        _long_slot[key] = make()
+    return _long_slot[key]
+
+
+def gcm_long_uniform(si):
+    """GCM_LONG_LENS of the session's ICV length, 16 consecutive records each;
+    tampered as gcm_uniform."""
+    def make():
+        rng = np.random.default_rng(8700 + si)
+        lens = GCM_LONG_LENS(GCM_SESSIONS[si][2])
+        cts = np.repeat(lens, GCM_RUN)
+        tamper = []
+        for r in range(1, len(lens), 2):
+            a = (r // 2) % GCM_RUN
+            b = (a + 1 + (r // 32) % (GCM_RUN - 1)) % GCM_RUN
+            tamper += [(r * GCM_RUN + a, "last"), (r * GCM_RUN + b, "icv")]
+        return make_batch(rng, [_gcm_sa(rng, si)], np.zeros(len(cts), dtype=np.int64), cts, tamper)
+    return _one_long(("gcm_long_uniform", si), make)
+
+
+def gcm_long_aligned(si):
+    """GCM_LONG_ALIGNED, 16 consecutive records each (every wave takes the
+    aligned schedule at 4 lanes); one ICV tampered in every second run."""
+    def make():
+        rng = np.random.default_rng(8750 + si)
+        cts = np.repeat(GCM_LONG_ALIGNED(), GCM_RUN)
+        tamper = [(r * GCM_RUN + (5 * r) % GCM_RUN, "icv") for r in range(1, len(cts) // GCM_RUN, 2)]
+        return make_batch(rng, [_gcm_sa(rng, si)], np.zeros(len(cts), dtype=np.int64), cts, tamper)
+    return _one_long(("gcm_long_aligned", si), make)
+
+
+def eta_long_uniform(kind):
+    """The kind's long set, 64 consecutive records each; even units intact
+    (the equal-length path of the verified decrypt at nbu up to 4093), three
+    records tampered in every odd one, as eta_uniform."""
+    def make():
+        rng = np.random.default_rng(8800 + list(ETA_KINDS).index(kind))
+        lens = eta_long_lens(kind)
+        cts = np.repeat(lens, ETA_UNIT)
+        tamper = []
+        for u in range(1, len(lens), 2):
+            a = (5 * u) % ETA_UNIT
+            tamper += [(u * ETA_UNIT + (a + 21 * k) % ETA_UNIT, w) for k, w in enumerate(("first", "last", "icv"))]
+        return make_batch(rng, [eta_sa(rng, kind)], np.zeros(len(cts), dtype=np.int64), cts, tamper)
+    return _one_long(("eta_long_uniform", kind), make)
+
+
+def _log_uniform(rng, lo, hi, step, size):
+    """Multiples of step in [lo, hi], their logarithm uniform."""
+    x = np.exp(rng.uniform(np.log(lo), np.log(hi + step), size))
+    return np.clip(x.astype(np.int64) // step * step, lo, hi)
+
+
+GCM_LONG_WAVES = 32
+ETA_LONG_UNITS = 8
+
+
+def gcm_long_mixed(foreign=True):
+    """32 waves of 16 records and 5 more, lengths log-uniform over 4..top, so
+    every lane of a wave rebuilds its counter cache at steps of its own.  In
+    every whole wave one record (its lane rotating) lies above 32 KiB and
+    another below 64 bytes.  Two sessions, one per aligned run of 256 records
+    (include/espgpu.h), guard bytes between the records, 5 % tampered anywhere,
+    some descriptors with len % 4 == 2 and (foreign=True: the grouped form)
+    some with the other session's id, neither at a multiple of four
+    (gcm_mixed) nor on a wave's two prescribed records."""
+    def make():
+        rng = np.random.default_rng(8900)
+        sas = [_gcm_sa(rng, 0), _gcm_sa(rng, 1)]
+        n = GCM_LONG_WAVES * GCM_RUN + 5
+        sa_idx = np.arange(n) // 256 % 2
+        tops = np.array([gcm_top(sas[s].mlen) for s in sa_idx])
+        cts = np.minimum(_log_uniform(rng, 4, tops.max(), 4, n), tops)
+        fixed = set()
+        for w in range(GCM_LONG_WAVES):
+            a, b = w * GCM_RUN + (7 * w) % GCM_RUN, w * GCM_RUN + (7 * w + 5) % GCM_RUN
+            cts[a] = _log_uniform(rng, 32772, tops[a], 4, 1)[0]
+            cts[b] = 4 * int(rng.integers(1, 16))
+            fixed |= {a, b}
+        free = np.array([i for i in range(n) if i % 4 and i not in fixed and i != n - 2])
+        picks = rng.choice(free, 24, replace=False)
+        other = {int(i): 1 - int(sa_idx[i]) for i in picks[:12]}
+        len_delta = {int(i): 2 for i in picks[12:]}
+        len_delta[n - 2] = 2                              # in the last, partial wave
+        tamper = [(int(i), "any") for i in np.nonzero(rng.random(n) < 0.05)[0]]
+        return make_batch(rng, sas, sa_idx, cts, tamper, stride_pad=8, len_delta=len_delta,
+                          foreign=other if foreign else None)
+    return _one_long(("gcm_long_mixed", foreign), make)
+
+
+def eta_long_mixed(kind):
+    """8 units of 64 records less 27, lengths log-uniform up to the kind's
+    largest (CBC: whole blocks), one record at the largest in every unit at a
+    rotating lane; 5 % tampered anywhere, and a few empty payloads, orphans and
+    CBC payloads shortened by 4 as eta_mixed("h-random")."""
+    def make():
+        rng = np.random.default_rng(9000 + list(ETA_KINDS).index(kind))
+        sas = [eta_sa(rng, kind)]
+        cbc = kind.startswith("cbc")
+        step, top = (16, eta_top(kind)) if cbc else (4, eta_top(kind))
+        n = ETA_LONG_UNITS * ETA_UNIT - 27
+        cts = _log_uniform(rng, step, top, step, n)
+        fixed = [u * ETA_UNIT + (9 * u + 3) % (ETA_UNIT - 27) for u in range(ETA_LONG_UNITS)]
+        cts[fixed] = top
+        free = np.array([i for i in range(n) if i not in fixed])
+        picks = rng.choice(free, 24, replace=False)
+        cts[picks[:8]] = 0
+        orphan = [int(i) for i in picks[8:16]]
+        len_delta = {int(i): -4 for i in picks[16:]} if cbc else {}
+        tamper = [(int(i), "any") for i in np.nonzero(rng.random(n) < 0.05)[0]]
+        return make_batch(rng, sas, np.zeros(n, dtype=np.int64), cts, tamper, stride_pad=4, len_delta=len_delta,
+                          orphan=orphan)
+    return _one_long(("eta_long_mixed", kind), make)

@@ -88,7 +88,9 @@ def test_the_families_cover_their_layouts():
     import ah_sweep_helpers as A
     import sweep_helpers as S
     gcm = B.runs_of("gcm")
-    assert len(gcm) == 3 * 3 * (len(S.GCM_SESSIONS) + len(S.GCM_FAMILIES))
+    assert len(gcm) == 3 * 3 * (len(S.GCM_SESSIONS) + len(S.GCM_FAMILIES) + 1)
+    assert len([r for r in gcm if r[0].startswith("gcm_long_mixed ")]) == 3 * 3
+    assert not any("long_uniform" in r[0] for fam in B.FAMILIES for r in B.runs_of(fam))
     assert {r[5][0] for r in gcm} == {"lanes4", "lanes8", "burst"}
     ah = B.runs_of("ah")
     assert len(ah) == 3 * 3 * len(A.HASH_ESN) + 3 + 6 + 1 + 3

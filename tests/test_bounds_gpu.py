@@ -78,9 +78,10 @@ def _assert_clean(rep):
 
 @pytest.mark.parametrize("mode", ["outofplace", "inplace", "encrypt"])
 def test_gcm(checked_lib, mode):
-    """gcm_uniform for the three GCM_SESSIONS and gcm_mixed over GCM_FAMILIES
-    in this mode, through each of the three designs (4 lanes, 8 lanes, burst;
-    set_tuning inside the child)."""
+    """gcm_uniform for the three GCM_SESSIONS, gcm_mixed over GCM_FAMILIES
+    and gcm_long_mixed (records up to 65532 bytes) in this mode, through each
+    of the three designs (4 lanes, 8 lanes, burst; set_tuning inside the
+    child)."""
     rep = _child(checked_lib, "gcm", mode)
     _assert_clean(rep)
     assert {r["label"].split(" ")[-1] for r in rep["runs"]} == {"lanes4", "lanes8", "burst"}

@@ -4,7 +4,12 @@ are 4-byte multiples: 65532 bytes, i.e. a 65535-byte IP datagram's ESP
 payload).  A 65532-byte GCM record runs 4093 counter blocks (the counter's
 low byte wraps 16 times: the counter cache is rebuilt mid-record); an ETA
 record runs 1023 HMAC-SHA1/256 or 512 SHA-512 blocks.  Bit-exact vs the
-oracle, tampered records EBADMSG."""
+oracle, tampered records EBADMSG.
+
+The maximum-length cases here are six records through the planner, decrypt
+only.  Whole waves and units of long records, every length around the
+counter-cache key changes and at the limit, encryption and trailer words are
+swept in test_long_records_gpu.py (layouts in sweep_helpers.py)."""
 import numpy as np
 import pytest
 

@@ -9,7 +9,11 @@ the lengths inside a wave differ as each family prescribes (see the layout
 functions).  Every case is decided by the oracle, byte for byte over the
 whole arena, the prefilled `out`, the statuses and the trailer words
 (sweep_helpers.check); a failure names the first differing record, its run
-or unit and its payload length."""
+or unit and its payload length.
+
+These sets end at 8224 bytes (GCM) and 1088 bytes (ETA).  Records from jumbo
+size to the 65532 bytes a descriptor carries are swept the same way in
+test_long_records_gpu.py."""
 import pytest
 
 import sweep_helpers as H
