@@ -13,6 +13,7 @@
 
 #include "decap.h"
 #include "espgpu.h"
+#include "ip_hdr.h"
 #include "rule_hd.h"
 
 namespace espgpu {
@@ -20,6 +21,9 @@ namespace espgpu {
 constexpr uint32_t kAhInKnown =
     ESPGPU_IN_TRANSPORT | ESPGPU_IN_TUNNEL | ESPGPU_IN_AF6 | ESPGPU_IN_AH | ESPGPU_IN_AH_KEEPTOS;
 constexpr uint32_t kAhSaveSlot = 64;                 // bytes of d_hsave per record: an IPv4 header with all its options fits
+
+// an ICV length the ABI allows
+ESPGPU_HD inline bool ah_mlen_usable(uint32_t mlen) { return mlen >= 4 && mlen <= 64 && !(mlen & 3); }
 
 // ah_hdrsiz (xform_ah.c:144-169): struct newah and the ICV, rounded up to 4
 // (RFC 4302) or, for an IPv6 SA, to 8.
@@ -59,8 +63,17 @@ ESPGPU_HD inline int ah_in_plan(uint32_t flags, uint32_t mlen, const uint8_t *pk
 // bytes [20, skip) of pkt: status, and on 0 bit j of *zero is set for every
 // option byte 20 + j that the massage zeroes.  The loop never reads a byte it
 // has zeroed, so it runs on the packet as it arrived and writes nothing.
-ESPGPU_HD inline int ah_opt_walk(const uint8_t *pkt, uint32_t skip, uint64_t *zero) {
+// OUT is the reference's `out`: the outbound walk also reports whether a
+// source-route option was seen and the last four bytes of the last one (the
+// hashed ip_dst, :362-365) as a memory-order dword, and refuses one shorter
+// than 4 bytes (a deliberate difference: its "last address" would start in
+// front of the option).  The inbound walk does neither.
+template <bool OUT>
+ESPGPU_HD inline int ah_opt_walk(const uint8_t *pkt, uint32_t skip, uint64_t *zero, bool *sr = nullptr,
+                                 uint32_t *srdst = nullptr) {
   uint64_t z = 0;
+  bool seen = false;
+  uint32_t last = 0;
   for (uint32_t off = 20; off < skip;) {
     const uint32_t o = pkt[off];
     if (o == 0) break;                                             // IPOPT_EOL, :315
@@ -73,10 +86,22 @@ ESPGPU_HD inline int ah_opt_walk(const uint8_t *pkt, uint32_t skip, uint64_t *ze
     if (count < 2) return ESPGPU_EINVAL;                           // :329, :344, :370
     const bool keep = o == 0x82 || o == 0x85 || o == 0x86 || o == 0x94 || o == 0x95;
     if (off + count > skip) return ESPGPU_EINVAL;                  // :386
+    if constexpr (OUT) {
+      if (o == 0x83 || o == 0x89) {                                // IPOPT_LSRR, IPOPT_SSRR
+        if (count < 4) return ESPGPU_EINVAL;
+        const uint8_t *q = pkt + off + count - 4;
+        last = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24;
+        seen = true;
+      }
+    }
     if (!keep) z |= ((1ull << count) - 1) << (off - 20);           // count <= 40 here
     off += count;
   }
   *zero = z;
+  if constexpr (OUT) {
+    *sr = seen;
+    *srdst = last;
+  }
   return 0;
 }
 
@@ -84,6 +109,28 @@ ESPGPU_HD inline int ah_opt_walk(const uint8_t *pkt, uint32_t skip, uint64_t *ze
 ESPGPU_HD inline uint32_t ah_spread4(uint32_t m) {
   return ((m & 1u) ? 0x000000ffu : 0u) | ((m & 2u) ? 0x0000ff00u : 0u) | ((m & 4u) ? 0x00ff0000u : 0u) |
          ((m & 8u) ? 0xff000000u : 0u);
+}
+
+// ah_massage_headers on the header in w[0..NW): the mutable fields zeroed
+// (:291-300, :404-419), the option bytes of `zero` too, and, outbound, the
+// destination replaced by a source route's last address.  The loop has a
+// constant bound so that the device keeps w[] in registers.
+template <uint32_t NW>
+ESPGPU_HD inline void ah_massage(uint32_t *w, bool af6, bool keeptos, uint64_t zero, bool sr = false,
+                                 uint32_t srdst = 0) {
+  if (af6) {
+    w[0] = 0x60u;                                                  // ip6_flow = 0, the version kept (:410-413)
+    w[1] &= 0x00ffffffu;                                           // ip6_hlim
+    if (ip6_linklocal(w[2])) w[2] &= 0x0000ffffu;                  // s6_addr16[1] of a link-local source (:416-419)
+    if (ip6_linklocal(w[6])) w[6] &= 0x0000ffffu;                  // ... destination
+  } else {
+    if (!keeptos) w[0] &= 0xffff00ffu;                             // ip_tos (V_ah_cleartos, :293)
+    w[1] &= 0x0000ffffu;                                           // ip_off (:297)
+    w[2] &= 0x0000ff00u;                                           // ip_ttl, ip_sum (:295-296)
+    if (sr) w[4] = srdst;                                          // :362-365
+#pragma unroll
+    for (uint32_t k = 5; k < NW; ++k) w[k] &= ~ah_spread4((uint32_t)(zero >> (4 * (k - 5))) & 0xfu);
+  }
 }
 
 // Checks 3 and 4 of espgpu_ah_input, after ah_in_plan returned 0.  NW is the
@@ -102,24 +149,13 @@ ESPGPU_HD inline int ah_in_massage(uint32_t flags, uint8_t *pkt, uint32_t skip, 
   if (flags & ESPGPU_IN_AF6) {
     if ((w[1] & 0xffffu) == 0) return ESPGPU_EMSGSIZE;             // ip6_plen == 0, xform_ah.c:404
   } else if (NW > 10) {
-    if (const int st = ah_opt_walk(pkt, skip, &zero)) return st;
+    if (const int st = ah_opt_walk<false>(pkt, skip, &zero)) return st;
   }
   // the header as it arrived (the front of xform_data, :632)
 #pragma unroll
   for (uint32_t k = 0; k < NW; ++k)
     if (k < nw) mem_st32(hsave + 4 * k, w[k]);
-  if (flags & ESPGPU_IN_AF6) {
-    w[0] = 0x60u;                                                  // ip6_flow = 0, the version kept (:410-413)
-    w[1] &= 0x00ffffffu;                                           // ip6_hlim
-    if ((w[2] & 0xc0ffu) == 0x80feu) w[2] &= 0x0000ffffu;          // s6_addr16[1] of a link-local source (:416-419)
-    if ((w[6] & 0xc0ffu) == 0x80feu) w[6] &= 0x0000ffffu;          // ... destination
-  } else {
-    if (!(flags & ESPGPU_IN_AH_KEEPTOS)) w[0] &= 0xffff00ffu;      // ip_tos (V_ah_cleartos, :293)
-    w[1] &= 0x0000ffffu;                                           // ip_off (:297)
-    w[2] &= 0x0000ff00u;                                           // ip_ttl, ip_sum (:295-296)
-#pragma unroll
-    for (uint32_t k = 5; k < NW; ++k) w[k] &= ~ah_spread4((uint32_t)(zero >> (4 * (k - 5))) & 0xfu);
-  }
+  ah_massage<NW>(w, flags & ESPGPU_IN_AF6, flags & ESPGPU_IN_AH_KEEPTOS, zero);
 #pragma unroll
   for (uint32_t k = 0; k < NW; ++k)
     if (k < nw) mem_st32(pkt + 4 * k, w[k]);

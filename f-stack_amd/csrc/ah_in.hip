@@ -25,13 +25,13 @@
 // session's mode and mlen and the AH header's first dword.  A tunnel record
 // never touches its packet or its save slot; a transport record loads its
 // 5-15 saved dwords into registers and stores them, fixed, ahsize bytes into
-// the packet.  The counters go through insa_book.h, as dcp_kernel's: no lane
+// the packet.  The counters go through sa_book.h, as dcp_kernel's: no lane
 // returns before its barrier.
 #include <hip/hip_runtime.h>
 
 #include "ah_in.h"
 #include "espgpu_internal.h"
-#include "insa_book.h"
+#include "sa_book.h"
 
 namespace espgpu {
 
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void ahd_kernel(AhdArgs a) {
     if (write) a.ipkt[i] = r;
     a.dstatus[i] = (uint8_t)st;
   }
-  insa_book_workgroup(a.in, sa, booked, accepted);   // key_sa_recordxfer
+  sa_book_workgroup(a.in, sa, booked, accepted);   // key_sa_recordxfer
 }
 
 }  // namespace

@@ -19,21 +19,21 @@
 // a variable.  The ballot stands where every lane of the wave reaches it, lanes
 // past n included; no shuffle, no barrier.
 //
-// ahf_*: frame.hip's five steps (validate, group, segment heads, frame,
-// commit) with ah_output's rule: every read of a counter precedes every write.
+// Step 2 is sa_group.h's five numbering steps (validate, group, segment heads,
+// frame, commit), shared with frame.hip, over ah_output's rule: every read of
+// a counter precedes every write.
 //
 // ahs_kernel: one lane per record; a qualifying lane loads its 5-15 saved
 // dwords into registers and stores them over the packet's.  The counters are
-// aggregated as snt_kernel aggregates its own (encap.hip; a copy, because
-// moving that code into a shared header changes the older kernels'
-// instructions): per wave one add pair per distinct SA, per workgroup one where
-// one SA has all of it.  Every lane of the wave stays on up to the barrier; the
-// shuffles stand outside every lane-dependent branch.
+// aggregated per wave and per workgroup before the 64-bit adds (sa_book.h,
+// shared with the other directions' closing kernels): no lane returns before
+// its barrier.
 #include <hip/hip_runtime.h>
 
 #include "ah_out.h"
 #include "dev_prims.h"
 #include "espgpu_internal.h"
+#include "sa_book.h"
 #include "sa_group.h"
 
 namespace espgpu {
@@ -98,82 +98,28 @@ __global__ __launch_bounds__(256) void aho_kernel(AhoArgs a) {
 }
 
 // ---- step 2 ---------------------------------------------------------------------
-struct AhfWs {
-  GroupWs g;
-  uint32_t *start;             // [nsa] grouped position of the SA's first record (SAs in the batch only)
-};
-
-struct AhfArgs {
+// ah_output's numbering rule for sa_group.h's steps.
+struct AhfRule {
   uint8_t *arena;
-  espgpu_desc *desc;
-  espgpu_outsa *out;
   const DevSA *sas;
-  uint8_t *fstatus;
-  const uint32_t *skey, *order;   // the sorted buffers
-  uint32_t n, nout, nsa, nsas;    // nsa = group_no_key(nout)
-  AhfWs w;
-};
+  uint32_t nsas;
 
-// Which records take part, and under which SA; the others are refused here.
-__global__ __launch_bounds__(256) void ahf_prep_kernel(AhfArgs a) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.n) return;
-  const espgpu_desc d = a.desc[i];
-  uint32_t k = a.nsa;
-  if (d.sa < a.nout && d.sa < a.nsas && a.sas[d.sa].mode == ESPGPU_CSP_MODE_DIGEST && ah_frame_takes(d.len, d.salt))
-    k = d.sa;
-  a.w.g.key[0][i] = k;
-  a.w.g.idx[0][i] = i;
-  a.fstatus[i] = k == a.nsa ? ESPGPU_EINVAL : 0;
-  if (k == a.nsa) a.desc[i].len = 0;
-}
+  static constexpr uint8_t kNoRoom = ESPGPU_EACCES;    // xform_ah.c:949
 
-__global__ __launch_bounds__(256) void ahf_heads_kernel(AhfArgs a) {
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= a.n) return;
-  const uint32_t key = a.skey[p];
-  if (key < a.nsa && (p == 0 || a.skey[p - 1] != key)) a.w.start[key] = p;
-}
-
-// One lane per grouped position: the record's number from its rank.
-__global__ __launch_bounds__(256) void ahf_frame_kernel(AhfArgs a) {
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= a.n) return;
-  const uint32_t key = a.skey[p];
-  if (key >= a.nsa) return;
-  const uint32_t i = a.order[p], rank = p - a.w.start[key];
-  const espgpu_outsa o = a.out[key];
-  if (rank >= ah_out_room(o.count, o.flags)) {        // the number space ended inside this batch (xform_ah.c:949)
-    a.fstatus[i] = ESPGPU_EACCES;
-    a.desc[i].len = 0;
-    return;
+  __device__ bool takes(const espgpu_desc &d, uint32_t, const espgpu_outsa *) const {
+    return d.sa < nsas && sas[d.sa].mode == ESPGPU_CSP_MODE_DIGEST && ah_frame_takes(d.len, d.salt);
   }
-  const uint64_t count = o.count + rank + 1;
-  const espgpu_desc d = a.desc[i];
-  ah_frame_write(a.arena + (size_t)d.off4 * 4, d.salt, o.spi, count);
-  a.desc[i].esn_hi = (o.flags & ESPGPU_OUT_ESN) ? (uint32_t)(count >> 32) : 0u;
-}
-
-// At the last grouped position of each SA: move its counter past what the
-// framing kernel gave out.
-__global__ __launch_bounds__(256) void ahf_commit_kernel(AhfArgs a) {
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  if (p >= a.n) return;
-  const uint32_t key = a.skey[p];
-  if (key >= a.nsa || (p + 1 < a.n && a.skey[p + 1] == key)) return;
-  const espgpu_outsa o = a.out[key];
-  const uint64_t k = (uint64_t)(p - a.w.start[key]) + 1, room = ah_out_room(o.count, o.flags);
-  const uint64_t m = k < room ? k : room;
-  if (m == 0) return;
-  a.out[key].count = o.count + m;
-}
-
-size_t ahf_carve(uint8_t *base, uint32_t n, uint32_t nout, AhfWs *w) {
-  WsCarver c{base};
-  group_carve(c, n, &w->g);
-  w->start = c.take<uint32_t>(group_no_key(nout));
-  return c.off;
-}
+  __device__ uint64_t room(const espgpu_outsa &o) const { return ah_out_room(o.count, o.flags); }
+  __device__ void write(espgpu_desc *dp, uint32_t, uint32_t, const espgpu_outsa &o, uint32_t rank) const {
+    const uint64_t count = o.count + rank + 1;
+    const espgpu_desc d = *dp;
+    ah_frame_write(arena + (size_t)d.off4 * 4, d.salt, o.spi, count);
+    dp->esn_hi = (o.flags & ESPGPU_OUT_ESN) ? (uint32_t)(count >> 32) : 0u;
+  }
+  __device__ void commit(espgpu_outsa *dst, const espgpu_outsa &o, uint32_t, uint64_t m) const {
+    dst->count = o.count + m;
+  }
+};
 
 // ---- step 5 ---------------------------------------------------------------------
 struct AhsArgs {
@@ -188,15 +134,8 @@ struct AhsArgs {
   uint32_t n, nenc, nsas;
 };
 
-constexpr uint32_t kAhsNone = 0xfffffffeu, kAhsMixed = 0xffffffffu;   // a wave's SA: no lane accepted; several SAs
-
-__device__ __forceinline__ void ahs_book(espgpu_encsa *enc, uint32_t sa, uint32_t bytes, uint32_t count) {
-  atomicAdd(reinterpret_cast<unsigned long long *>(&enc[sa].bytes), (unsigned long long)bytes);
-  atomicAdd(reinterpret_cast<unsigned long long *>(&enc[sa].packets), (unsigned long long)count);
-}
-
 __global__ __launch_bounds__(256) void ahs_kernel(AhsArgs a) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t sa = 0, booked = 0;
   bool accepted = false;
   if (i < a.n) {
@@ -216,50 +155,7 @@ __global__ __launch_bounds__(256) void ahs_kernel(AhsArgs a) {
     }
     a.sstatus[i] = (uint8_t)st;
   }
-  // key_sa_recordxfer (ipsec_output.c:770), as snt_kernel's
-  __shared__ uint32_t s_sa[4], s_bytes[4], s_count[4];
-  const uint32_t wave = threadIdx.x >> 6;
-  unsigned long long m = __ballot(accepted);
-  const uint32_t lead = m ? (uint32_t)__ffsll((long long)m) - 1 : 0u;
-  const uint32_t lsa = __shfl(sa, lead);
-  const bool mine = accepted && sa == lsa;
-  const unsigned long long mm = __ballot(mine);
-  const uint32_t bytes = wave_sum(mine ? booked : 0u);         // 64 lanes of < 2^16 each
-  const uint32_t count = (uint32_t)__popcll(mm);
-  if (lane == 0) {
-    s_sa[wave] = m == 0 ? kAhsNone : mm == m ? lsa : kAhsMixed;
-    s_bytes[wave] = bytes;
-    s_count[wave] = count;
-  }
-  __syncthreads();
-  uint32_t wsa = kAhsNone, wbytes = 0, wcount = 0;
-  bool one = true;
-  for (uint32_t w = 0; w < 4; ++w) {
-    const uint32_t v = s_sa[w];
-    if (v == kAhsNone) continue;
-    if (v == kAhsMixed || (wsa != kAhsNone && v != wsa)) one = false;
-    wsa = v;
-    wbytes += s_bytes[w];
-    wcount += s_count[w];
-  }
-  if (one) {
-    if (threadIdx.x == 0 && wsa != kAhsNone) ahs_book(a.enc, wsa, wbytes, wcount);
-    return;
-  }
-  // otherwise per wave: the leading SA is summed already, then the loop over
-  // the other distinct SAs among the accepted lanes (m is wave-uniform)
-  if (m == 0) return;
-  if (lane == lead) ahs_book(a.enc, lsa, bytes, count);
-  m &= ~mm;
-  while (m) {
-    const uint32_t ld = (uint32_t)__ffsll((long long)m) - 1;
-    const uint32_t nsa = __shfl(sa, ld);
-    const bool hit = accepted && sa == nsa;
-    const unsigned long long hm = __ballot(hit);
-    const uint32_t b = wave_sum(hit ? booked : 0u);
-    if (lane == ld) ahs_book(a.enc, nsa, b, (uint32_t)__popcll(hm));
-    m &= ~hm;
-  }
+  sa_book_workgroup(a.enc, sa, booked, accepted);   // key_sa_recordxfer (ipsec_output.c:770)
 }
 
 }  // namespace
@@ -273,35 +169,12 @@ int launch_ah_encap(uint8_t *arena, const espgpu_pkt *pkt, const uint16_t *sa, u
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-size_t ah_frame_workspace_bytes(uint32_t n, uint32_t nout) {
-  AhfWs w;
-  return ahf_carve(nullptr, n, nout, &w);
-}
+size_t ah_frame_workspace_bytes(uint32_t n, uint32_t nout) { return num_workspace_bytes(n, nout); }
 
 int launch_ah_frame(uint8_t *arena, espgpu_desc *desc, uint32_t n, espgpu_outsa *out, uint32_t nout,
                     const DevSA *sas, uint32_t nsas, uint8_t *fstatus, void *ws, void *stream) {
-  if (n == 0) return 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 blk(256), grid_n((n + 255) / 256);
-  AhfArgs a{};
-  a.arena = arena;
-  a.desc = desc;
-  a.out = out;
-  a.sas = sas;
-  a.fstatus = fstatus;
-  a.n = n;
-  a.nout = nout;
-  a.nsa = group_no_key(nout);
-  a.nsas = nsas;
-  ahf_carve(static_cast<uint8_t *>(ws), n, nout, &a.w);
-  hipLaunchKernelGGL(ahf_prep_kernel, grid_n, blk, 0, st, a);
-  const int cur = group_by_key(a.w.g, n, a.nsa, st);
-  a.skey = a.w.g.key[cur];
-  a.order = a.w.g.idx[cur];
-  hipLaunchKernelGGL(ahf_heads_kernel, grid_n, blk, 0, st, a);
-  hipLaunchKernelGGL(ahf_frame_kernel, grid_n, blk, 0, st, a);
-  hipLaunchKernelGGL(ahf_commit_kernel, grid_n, blk, 0, st, a);
-  return hipGetLastError() == hipSuccess ? 0 : -1;
+  const AhfRule r = {arena, sas, nsas};
+  return num_batch(r, desc, n, out, nout, fstatus, ws, reinterpret_cast<hipStream_t>(stream));
 }
 
 int launch_ah_sent(uint8_t *arena, const espgpu_pkt *opkt, const espgpu_desc *desc, const uint8_t *status, uint32_t n,

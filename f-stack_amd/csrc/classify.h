@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "espgpu.h"
+#include "ip_hdr.h"
 #include "rule_hd.h"
 
 namespace espgpu {
@@ -24,8 +25,7 @@ ESPGPU_HD inline uint32_t key_u32hash(uint32_t spi) {
 constexpr uint32_t kClsKnown = ESPGPU_CLS_IPCSUM | ESPGPU_CLS_AH | 0xffff0000u;   // and ESPGPU_CLS_NATT_PORT's bits
 
 ESPGPU_HD inline uint32_t cls_bswap32(uint32_t x) { return __builtin_bswap32(x); }
-// the big-endian 16-bit field in the low / the high half of a memory-order dword
-ESPGPU_HD inline uint32_t cls_be16lo(uint32_t w) { return ((w & 0xffu) << 8) | ((w >> 8) & 0xffu); }
+// the big-endian 16-bit field in the high half of a memory-order dword (the low half's is ip_be16)
 ESPGPU_HD inline uint32_t cls_be16hi(uint32_t w) { return ((w >> 8) & 0xff00u) | (w >> 24); }
 
 // The first half of a slot: SPI, sa | proto << 16 | af << 24, salt, flags.  One
@@ -111,11 +111,7 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
         // order up to a byte swap, and 0xffff is its own swap (in_cksum)
         uint64_t acc = (uint64_t)w0 + w1 + w2 + w3 + w4;
         for (uint32_t k = 5; k < ihl; ++k) acc += mem_ld32(pkt + 4 * k);
-        acc = (acc & 0xffffffffu) + (acc >> 32);
-        acc = (acc & 0xffffu) + ((acc >> 16) & 0xffffu) + (acc >> 32);
-        acc = (acc & 0xffffu) + (acc >> 16);
-        acc = (acc & 0xffffu) + (acc >> 16);
-        if (acc != 0xffffu) break;
+        if (ip_fold16(acc) != 0xffffu) break;
       }
       const uint32_t ip_len = cls_be16hi(w0);
       if (ip_len < hlen || ip_len > len) break;
@@ -126,7 +122,7 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
         // udp_input up to the UF_ESPINUDP socket, then udp_ipsec_input
         if (ip_len - hlen < 8) break;                  // no UDP header: an ordinary datagram's error
         uports = mem_ld32(pkt + hlen);
-        const uint32_t u1 = mem_ld32(pkt + hlen + 4), ulen = cls_be16lo(u1);
+        const uint32_t u1 = mem_ld32(pkt + hlen + 4), ulen = ip_be16(u1);
         if (cls_be16hi(uports) != port) break;         // another socket's, udp_usrreq.c:335
         st = ESPGPU_EINVAL;
         if (ulen < 8 || ulen > ip_len - hlen) break;   // :468-472; a longer ip_len is trimmed, :474
@@ -161,7 +157,7 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
       }
     } else if (ver == 6) {                             // ip6_input, ipsec6_input
       if (len < 40) break;
-      const uint32_t plen = cls_be16lo(w1);
+      const uint32_t plen = ip_be16(w1);
       st = ESPGPU_ENOTSUP;
       if (plen == 0) break;                            // jumbogram
       st = ESPGPU_EINVAL;
@@ -171,7 +167,7 @@ ESPGPU_HD inline int esp_classify_rule(const espgpu_sad_entry *table, uint32_t n
       ah = nxt == 51 && (flags & ESPGPU_CLS_AH);
       if (nxt != 50 && !ah) break;
       for (uint32_t j = 0; j < 4; ++j) dst[j] = mem_ld32(pkt + 24 + 4 * j);
-      if ((dst[0] & 0xc0ffu) == 0x80feu) break;        // fe80::/10
+      if (ip6_linklocal(dst[0])) break;
       st = ESPGPU_EINVAL;
       if (ah) {
         if (plen < 12) break;

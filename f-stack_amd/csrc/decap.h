@@ -9,15 +9,13 @@
 #include <stdint.h>
 
 #include "espgpu.h"
+#include "ip_hdr.h"
 #include "rule_hd.h"
 
 namespace espgpu {
 
 constexpr uint32_t kInKnown =
     ESPGPU_IN_TRANSPORT | ESPGPU_IN_TUNNEL | ESPGPU_IN_PAD_RAND | ESPGPU_IN_AF6 | ESPGPU_IN_NATT;
-
-// a 16-bit value as the big-endian field in one half of a memory-order dword
-ESPGPU_HD inline uint32_t dcp_be16(uint32_t x) { return ((x & 0xffu) << 8) | ((x >> 8) & 0xffu); }
 
 // What the rule decides without the packet: checks 1-3, and the result and
 // the booked bytes of checks 4 and 5.
@@ -86,22 +84,12 @@ ESPGPU_HD inline int dcp_transport(const uint8_t *src, uint8_t *dst, uint32_t fl
   if (flags & ESPGPU_IN_AF6) {
     if (((w[0] >> 4) & 0xfu) != 6) return ESPGPU_EINVAL;
     // ip6_plen (ipsec_input.c:532), ip6_nxt (xform_esp.c:636); the hop limit stays
-    w[1] = (w[1] & 0xff000000u) | p.nxt << 16 | dcp_be16(p.q & 0xffffu);
+    w[1] = (w[1] & 0xff000000u) | p.nxt << 16 | ip_be16(p.q & 0xffffu);
   } else {
     if ((w[0] & 0xffu) != (0x40u | nw)) return ESPGPU_EINVAL;
-    w[0] = (w[0] & 0xffffu) | dcp_be16((skip - u + p.q) & 0xffffu) << 16;        // ip_len, :312
+    w[0] = (w[0] & 0xffffu) | ip_be16((skip - u + p.q) & 0xffffu) << 16;         // ip_len, :312
     w[2] = (w[2] & 0x000000ffu) | p.nxt << 8;                                    // ip_p; ip_sum = 0, :313
-    // in_cksum over the header (:314): the one's-complement sum of the 16-bit
-    // words is the same in either byte order up to a byte swap, so the sum of
-    // the memory-order halves goes back into a memory-order half
-    uint64_t acc = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 15; ++k) acc += w[k];
-    acc = (acc & 0xffffffffu) + (acc >> 32);
-    acc = (acc & 0xffffu) + ((acc >> 16) & 0xffffu) + (acc >> 32);
-    acc = (acc & 0xffffu) + (acc >> 16);
-    acc = (acc & 0xffffu) + (acc >> 16);
-    w[2] |= (~(uint32_t)acc & 0xffffu) << 16;
+    w[2] |= ip_hdr_cksum<15>(w) << 16;                                           // in_cksum, :314
   }
 #pragma unroll
   for (uint32_t k = 0; k < 15; ++k)

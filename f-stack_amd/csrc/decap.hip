@@ -13,14 +13,14 @@
 // them hlen bytes further on.
 //
 // The SA counters are aggregated per wave and per workgroup before the 64-bit
-// adds (insa_book.h, shared with the AH decapsulation).
+// adds (sa_book.h, shared with the AH decapsulation).
 #include <hip/hip_runtime.h>
 
 #include "decap.h"
 #include "dev_prims.h"
 #include "espgpu_internal.h"
 #include "frame.h"
-#include "insa_book.h"
+#include "sa_book.h"
 
 namespace espgpu {
 
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void dcp_kernel(DcpArgs a) {
     a.ipkt[i] = r;
     a.dstatus[i] = (uint8_t)st;
   }
-  insa_book_workgroup(a.in, sa, booked, accepted);   // key_sa_recordxfer
+  sa_book_workgroup(a.in, sa, booked, accepted);   // key_sa_recordxfer
 }
 
 }  // namespace

@@ -17,22 +17,16 @@
 // headroom, pkt + len + tailroom) of one batch apart, so no lane writes what
 // another reads.
 //
-// snt_kernel: one lane per record; the counters are aggregated as dcp_kernel
-// aggregates its own (decap.hip; kept as a copy here because moving that code
-// into a shared header changed dcp_kernel's instructions).  Per wave: for each
-// distinct SA among the accepted lanes (ballot, the first such lane's SA
-// broadcast, the matching lanes' bytes summed across the wave) one lane issues
-// one 64-bit add pair; a workgroup whose accepted records all belong to one SA
-// adds once for its four waves, through 48 bytes of LDS.  All of it runs with
-// every lane of the wave on: the conditions are ballots or workgroup-uniform,
-// no lane returns before the barrier, and the shuffles stand outside every
-// lane-dependent branch.
+// snt_kernel: one lane per record; the counters are aggregated per wave and
+// per workgroup before the 64-bit adds (sa_book.h, shared with the other
+// directions' closing kernels): no lane returns before its barrier.
 #include <hip/hip_runtime.h>
 
 #include "dev_prims.h"
 #include "encap.h"
 #include "espgpu_internal.h"
 #include "frame.h"
+#include "sa_book.h"
 
 namespace espgpu {
 
@@ -88,15 +82,8 @@ struct SntArgs {
   uint32_t n, nenc;
 };
 
-constexpr uint32_t kSntNone = 0xfffffffeu, kSntMixed = 0xffffffffu;   // a wave's SA: no lane accepted; several SAs
-
-__device__ __forceinline__ void snt_book(espgpu_encsa *enc, uint32_t sa, uint32_t bytes, uint32_t count) {
-  atomicAdd(reinterpret_cast<unsigned long long *>(&enc[sa].bytes), (unsigned long long)bytes);
-  atomicAdd(reinterpret_cast<unsigned long long *>(&enc[sa].packets), (unsigned long long)count);
-}
-
 __global__ __launch_bounds__(256) void snt_kernel(SntArgs a) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63u;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t sa = 0, booked = 0;
   bool accepted = false;
   if (i < a.n) {
@@ -106,52 +93,7 @@ __global__ __launch_bounds__(256) void snt_kernel(SntArgs a) {
     // key_sa_recordxfer runs before the UDP header exists (ipsec_output.c:770, :808)
     if (accepted && (a.enc[sa].flags & ESPGPU_ENC_NATT)) booked -= 8;
   }
-  // key_sa_recordxfer (ipsec_output.c:770).  Each wave first sums its leading
-  // SA (the SA of its first accepted lane); when that covers every accepted
-  // lane of every wave of the workgroup, one lane adds for all 256 records.
-  __shared__ uint32_t s_sa[4], s_bytes[4], s_count[4];
-  const uint32_t wave = threadIdx.x >> 6;
-  unsigned long long m = __ballot(accepted);
-  const uint32_t lead = m ? (uint32_t)__ffsll((long long)m) - 1 : 0u;
-  const uint32_t lsa = __shfl(sa, lead);
-  const bool mine = accepted && sa == lsa;
-  const unsigned long long mm = __ballot(mine);
-  const uint32_t bytes = wave_sum(mine ? booked : 0u);         // 64 lanes of < 2^16 each
-  const uint32_t count = (uint32_t)__popcll(mm);
-  if (lane == 0) {
-    s_sa[wave] = m == 0 ? kSntNone : mm == m ? lsa : kSntMixed;
-    s_bytes[wave] = bytes;
-    s_count[wave] = count;
-  }
-  __syncthreads();
-  uint32_t wsa = kSntNone, wbytes = 0, wcount = 0;
-  bool one = true;
-  for (uint32_t w = 0; w < 4; ++w) {
-    const uint32_t v = s_sa[w];
-    if (v == kSntNone) continue;
-    if (v == kSntMixed || (wsa != kSntNone && v != wsa)) one = false;
-    wsa = v;
-    wbytes += s_bytes[w];
-    wcount += s_count[w];
-  }
-  if (one) {
-    if (threadIdx.x == 0 && wsa != kSntNone) snt_book(a.enc, wsa, wbytes, wcount);
-    return;
-  }
-  // otherwise per wave: the leading SA is summed already, then the loop over
-  // the other distinct SAs among the accepted lanes
-  if (m == 0) return;
-  if (lane == lead) snt_book(a.enc, lsa, bytes, count);
-  m &= ~mm;
-  while (m) {
-    const uint32_t ld = (uint32_t)__ffsll((long long)m) - 1;
-    const uint32_t nsa = __shfl(sa, ld);
-    const bool hit = accepted && sa == nsa;
-    const unsigned long long hm = __ballot(hit);
-    const uint32_t b = wave_sum(hit ? booked : 0u);
-    if (lane == ld) snt_book(a.enc, nsa, b, (uint32_t)__popcll(hm));
-    m &= ~hm;
-  }
+  sa_book_workgroup(a.enc, sa, booked, accepted);   // key_sa_recordxfer (ipsec_output.c:770)
 }
 
 }  // namespace

@@ -453,11 +453,10 @@ int espgpu_esp_decap_batch(espgpu_ctx *c, const uint8_t *d_arena, uint8_t *d_out
 // ah_input's checks and ah_massage_headers for one packet, and ah_input_cb's
 // tail with ipsec4/6_common_input_cb.  The rules espgpu_ah_input_batch and
 // espgpu_ah_decap_batch apply (ah_in.h).
-static bool ah_mlen_ok(uint32_t mlen) { return mlen >= 4 && mlen <= 64 && !(mlen & 3); }
 
 int espgpu_ah_input(const espgpu_insa *in, uint32_t mlen, uint8_t *pkt, uint32_t len, uint32_t salt,
                     uint8_t *hsave) {
-  if (!in || !pkt || !hsave || !ah_mlen_ok(mlen)) return ESPGPU_EINVAL;
+  if (!in || !pkt || !hsave || !ah_mlen_usable(mlen)) return ESPGPU_EINVAL;
   return ah_input_rule(in->flags, mlen, pkt, len, salt, hsave);
 }
 
@@ -477,7 +476,7 @@ int espgpu_ah_decap(espgpu_insa *in, uint32_t mlen, uint8_t *pkt, uint32_t len, 
                     uint32_t *out_off, uint32_t *out_len) {
   if (out_off) *out_off = 0;
   if (out_len) *out_len = 0;
-  if (!in || !pkt || !hsave || !out_off || !out_len || !ah_mlen_ok(mlen)) return ESPGPU_EINVAL;
+  if (!in || !pkt || !hsave || !out_off || !out_len || !ah_mlen_usable(mlen)) return ESPGPU_EINVAL;
   DecapPlan p;
   const int st = ah_decap_rule(in->flags, mlen, pkt, len, salt, hsave, &p);
   if (st) return st;

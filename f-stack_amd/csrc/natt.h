@@ -8,13 +8,14 @@
 //
 // All sums are over memory-order dwords: the one's-complement sum of the
 // 16-bit words is the same in either byte order up to a byte swap, so a sum of
-// memory-order halves goes back into a memory-order half (decap.h's idiom),
+// memory-order halves goes back into a memory-order half (ip_hdr.h's fold),
 // and sav->natt->cksum is kept as the value the reference adds to the field's
 // two bytes as they lie in memory.
 #pragma once
 #include <stdint.h>
 
 #include "espgpu.h"
+#include "ip_hdr.h"
 #include "rule_hd.h"
 
 namespace espgpu {
@@ -26,25 +27,12 @@ namespace espgpu {
 // stays until that is repeated at other packet sizes.
 constexpr uint32_t kNattLanes = 16;
 
-// REDUCE16 with ADDCARRY (amd64/in_cksum.c:61-73): a 64-bit sum of dwords to
-// 16 bits.  0 only for a sum of 0; every other multiple of 65535 gives 0xffff.
-ESPGPU_HD inline uint32_t natt_fold(uint64_t acc) {
-  acc = (acc & 0xffffffffu) + (acc >> 32);
-  acc = (acc & 0xffffu) + ((acc >> 16) & 0xffffu) + (acc >> 32);
-  acc = (acc & 0xffffu) + (acc >> 16);
-  acc = (acc & 0xffffu) + (acc >> 16);
-  return (uint32_t)acc;
-}
-
 // in_addword (in_cksum.c:174-181)
 ESPGPU_HD inline uint32_t natt_addword(uint32_t a, uint32_t b) {
   uint32_t sum = a + b;
   if (sum > 65535) sum -= 65535;
   return sum;
 }
-
-// a 16-bit value as the big-endian field in one half of a memory-order dword (htons)
-ESPGPU_HD inline uint32_t natt_be16(uint32_t x) { return ((x & 0xffu) << 8) | ((x >> 8) & 0xffu); }
 
 // Where the fix works in a packet that takes part.
 struct NattPlan {
@@ -95,8 +83,7 @@ ESPGPU_HD inline bool natt_plan(const uint8_t *pkt, uint32_t len, uint32_t proto
   p->pseudo = 0;
   if (policy == 0) return true;
   if (proto == 17) {                                   // ip_output.c:1068-1078
-    const uint32_t w = mem_ld32(pkt + ihl + 4);
-    const uint32_t ulen = ((w & 0xffu) << 8) | ((w >> 8) & 0xffu);
+    const uint32_t ulen = ip_be16(mem_ld32(pkt + ihl + 4));
     // the reference would sum past the mbuf (or sum nothing the field is in): left alone
     if (ulen < 8 || ulen > seg) return false;
     p->cklen = ulen;
@@ -106,8 +93,8 @@ ESPGPU_HD inline bool natt_plan(const uint8_t *pkt, uint32_t len, uint32_t proto
     p->cklen = seg;
   }
   // in_pseudo's three addends (udpencap.c:284-285); folded with the rest
-  const uint64_t ps = (uint64_t)mem_ld32(pkt + 12) + mem_ld32(pkt + 16) + natt_be16(seg + proto);
-  p->pseudo = natt_fold(ps);
+  const uint64_t ps = (uint64_t)mem_ld32(pkt + 12) + mem_ld32(pkt + 16) + ip_be16(seg + proto);
+  p->pseudo = ip_fold16(ps);
   return true;
 }
 
@@ -149,7 +136,7 @@ ESPGPU_HD inline uint32_t natt_dword(const uint8_t *seg, uint32_t k, uint32_t ck
 // pseudo-header sum, so 0x0000 and 0xffff come out as the reference's do.
 ESPGPU_HD inline void natt_finish(uint8_t *pkt, const NattPlan &p, uint64_t sum) {
   const uint32_t old = natt_ld_field(pkt, p.fat);
-  uint32_t csum = ~natt_fold((uint64_t)natt_fold(sum) + p.pseudo + (0xffffu - old)) & 0xffffu;
+  uint32_t csum = ~ip_fold16((uint64_t)ip_fold16(sum) + p.pseudo + (0xffffu - old)) & 0xffffu;
   if (p.proto == 17 && csum == 0) csum = 0xffffu;      // ip_output.c:1079-1080
   natt_st_field(pkt, p.fat, csum);
 }

@@ -1,5 +1,5 @@
-// rule_hd.h — what the rule headers (classify.h, decap.h, encap.h, frame.h, replay.h)
-// share: the marker that makes one function serve the host entry point and the
+// rule_hd.h — what the rule headers (classify.h, decap.h, encap.h, frame.h, replay.h,
+// ah_in.h, ah_out.h, natt.h, ip_hdr.h) share: the marker that makes one function serve the host entry point and the
 // kernel, and a packet dword in memory order.  Plain C++ with no HIP header.
 #pragma once
 #include <stdint.h>

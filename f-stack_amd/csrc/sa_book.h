@@ -1,6 +1,7 @@
-// insa_book.h — key_sa_recordxfer for a workgroup of the inbound decapsulation
-// kernels (decap.hip dcp_kernel, ah_in.hip ahd_kernel): every accepted lane's
-// bytes and one packet into its SA's espgpu_insa.
+// sa_book.h — key_sa_recordxfer for a workgroup of the kernels that close a
+// direction (decap.hip dcp_kernel, ah_in.hip ahd_kernel, encap.hip snt_kernel,
+// ah_out.hip ahs_kernel): every accepted lane's bytes and one packet into its
+// SA's lifetime counters, espgpu_insa's inbound and espgpu_encsa's outbound.
 //
 // The counters are aggregated per wave: for each distinct SA among the
 // accepted lanes (ballot, the first such lane's SA broadcast, the matching
@@ -22,19 +23,21 @@ namespace espgpu {
 
 namespace {
 
-constexpr uint32_t kDcpNone = 0xfffffffeu, kDcpMixed = 0xffffffffu;   // a wave's SA: no lane accepted; several SAs
+constexpr uint32_t kBookNone = 0xfffffffeu, kBookMixed = 0xffffffffu;   // a wave's SA: no lane accepted; several SAs
 
-__device__ __forceinline__ void dcp_book(espgpu_insa *in, uint32_t sa, uint32_t bytes, uint32_t count) {
-  atomicAdd(reinterpret_cast<unsigned long long *>(&in[sa].bytes), (unsigned long long)bytes);
-  atomicAdd(reinterpret_cast<unsigned long long *>(&in[sa].packets), (unsigned long long)count);
+template <class SA>
+__device__ __forceinline__ void sa_book(SA *sas, uint32_t sa, uint32_t bytes, uint32_t count) {
+  atomicAdd(reinterpret_cast<unsigned long long *>(&sas[sa].bytes), (unsigned long long)bytes);
+  atomicAdd(reinterpret_cast<unsigned long long *>(&sas[sa].packets), (unsigned long long)count);
 }
 
 // Called by every thread of a 256-thread workgroup, as the last thing the
-// kernel does: `accepted` lanes book `booked` bytes (< 2^17) into in[sa].
+// kernel does: `accepted` lanes book `booked` bytes (< 2^17) into sas[sa].
 // Each wave first sums its leading SA (the SA of its first accepted lane);
 // when that covers every accepted lane of every wave of the workgroup, one
 // lane adds for all 256 records.
-__device__ __forceinline__ void insa_book_workgroup(espgpu_insa *in, uint32_t sa, uint32_t booked, bool accepted) {
+template <class SA>
+__device__ __forceinline__ void sa_book_workgroup(SA *sas, uint32_t sa, uint32_t booked, bool accepted) {
   __shared__ uint32_t s_sa[4], s_bytes[4], s_count[4];
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   unsigned long long m = __ballot(accepted);
@@ -45,29 +48,29 @@ __device__ __forceinline__ void insa_book_workgroup(espgpu_insa *in, uint32_t sa
   const uint32_t bytes = wave_sum(mine ? booked : 0u);         // 64 lanes of < 2^17 each
   const uint32_t count = (uint32_t)__popcll(mm);
   if (lane == 0) {
-    s_sa[wave] = m == 0 ? kDcpNone : mm == m ? lsa : kDcpMixed;
+    s_sa[wave] = m == 0 ? kBookNone : mm == m ? lsa : kBookMixed;
     s_bytes[wave] = bytes;
     s_count[wave] = count;
   }
   __syncthreads();
-  uint32_t wsa = kDcpNone, wbytes = 0, wcount = 0;
+  uint32_t wsa = kBookNone, wbytes = 0, wcount = 0;
   bool one = true;
   for (uint32_t w = 0; w < 4; ++w) {
     const uint32_t v = s_sa[w];
-    if (v == kDcpNone) continue;
-    if (v == kDcpMixed || (wsa != kDcpNone && v != wsa)) one = false;
+    if (v == kBookNone) continue;
+    if (v == kBookMixed || (wsa != kBookNone && v != wsa)) one = false;
     wsa = v;
     wbytes += s_bytes[w];
     wcount += s_count[w];
   }
   if (one) {
-    if (threadIdx.x == 0 && wsa != kDcpNone) dcp_book(in, wsa, wbytes, wcount);
+    if (threadIdx.x == 0 && wsa != kBookNone) sa_book(sas, wsa, wbytes, wcount);
     return;
   }
   // otherwise per wave: the leading SA is summed already, then the loop over
-  // the other distinct SAs among the accepted lanes
+  // the other distinct SAs among the accepted lanes (m is wave-uniform)
   if (m == 0) return;
-  if (lane == lead) dcp_book(in, lsa, bytes, count);
+  if (lane == lead) sa_book(sas, lsa, bytes, count);
   m &= ~mm;
   while (m) {
     const uint32_t ld = (uint32_t)__ffsll((long long)m) - 1;
@@ -75,7 +78,7 @@ __device__ __forceinline__ void insa_book_workgroup(espgpu_insa *in, uint32_t sa
     const bool hit = accepted && sa == nsa;
     const unsigned long long hm = __ballot(hit);
     const uint32_t b = wave_sum(hit ? booked : 0u);
-    if (lane == ld) dcp_book(in, nsa, b, (uint32_t)__popcll(hm));
+    if (lane == ld) sa_book(sas, nsa, b, (uint32_t)__popcll(hm));
     m &= ~hm;
   }
 }

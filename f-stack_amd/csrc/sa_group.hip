@@ -98,7 +98,20 @@ __global__ __launch_bounds__(256) void grp_scatter_kernel(const uint32_t *key_in
   }
 }
 
+// One lane per grouped position: where a key's segment starts.
+__global__ __launch_bounds__(256) void grp_heads_kernel(const uint32_t *skey, uint32_t *start, uint32_t n,
+                                                        uint32_t nokey) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= n) return;
+  const uint32_t key = skey[p];
+  if (key < nokey && (p == 0 || skey[p - 1] != key)) start[key] = p;
+}
+
 }  // namespace
+
+void group_heads(const uint32_t *skey, uint32_t *start, uint32_t n, uint32_t nokey, hipStream_t st) {
+  hipLaunchKernelGGL(grp_heads_kernel, dim3((n + 255) / 256), dim3(256), 0, st, skey, start, n, nokey);
+}
 
 int group_by_key(const GroupWs &g, uint32_t n, uint32_t nokey, hipStream_t st) {
   const dim3 blk(256), tiles(g.sort_tiles);

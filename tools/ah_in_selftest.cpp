@@ -214,7 +214,7 @@ void option_refusals() {
         Heap hd(skip);
         memcpy(hd.p, orig.data(), skip);
         uint64_t z = 0;
-        CHECK(ah_opt_walk(hd.p, skip, &z) == ESPGPU_EINVAL);
+        CHECK(ah_opt_walk<false>(hd.p, skip, &z) == ESPGPU_EINVAL);
         // EOL or NOP in that last byte: accepted
         for (uint8_t last : {(uint8_t)0, (uint8_t)1}) {
           memcpy(pk.p, orig.data(), len);

@@ -290,7 +290,7 @@ void option_refusals() {
         uint64_t z = 0;
         bool sr = false;
         uint32_t d = 0;
-        CHECK(ah_opt_walk_out(hd.p, skip, &z, &sr, &d) == ESPGPU_EINVAL);
+        CHECK(ah_opt_walk<true>(hd.p, skip, &z, &sr, &d) == ESPGPU_EINVAL);
         // EOL or NOP in that last byte: accepted
         for (uint8_t last : {(uint8_t)0, (uint8_t)1}) {
           memcpy(blk.p, orig.data(), front + len);
